@@ -7,11 +7,22 @@ all-reduce that gives every rank the full score vector. Every particle of the
 timed steps is interior (SURVEY.md §8d fixed-work variant), so no evaluation
 takes the sentinel short-cut. value = swarm x steps / wall time of the timed
 region, max over ranks; at N GPUs the swarm is 64 particles per GPU (weak
-scaling). The real PSO update loop, whose box-clipped particles are free
-sentinels, is timed separately and reported under "pso_loop".
+scaling).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--n 4096] [--d 3] [--swarm-per-gpu P]
-                    [--no-cpu] [--plumbing]
+                    [--dump-outputs DIR] [--full] [--no-cpu] [--plumbing]
+
+A plain run does only what the headline figure needs: set up, W warm-up steps, the K timed
+steps, the `--dump-outputs` files, the JSON line. `--dump-outputs DIR` writes what the last
+timed step returned to its caller, the swarm's full score vector, as DIR/scores.npy (float64);
+the data and the particle batches come from `--seed`, so the same arguments give the same
+inputs on every run and two builds can be compared output for output.
+
+`--full` adds everything else to the same line: the second, profiled pass of the K steps with
+the roofline and per-kernel breakdown, the GEMM-core and dense-MFMA ceilings, the real PSO
+update loop (whose box-clipped particles are free sentinels; "pso_loop"), the other BASELINE
+configs, the prediction / probability-surface / hull / KMeans lines and the CPU baselines
+(the `--no-*` / `--*-points` options trim those legs and mean nothing without `--full`).
 
 N > 1: one process per GPU. Under a launcher (torchrun: RANK / WORLD_SIZE / LOCAL_RANK set)
 this process is one rank; without one, `--gpus N` starts the N rank processes itself before
@@ -20,7 +31,7 @@ batch) and the barrier / max-over-ranks timing go through libgpfit's own RCCL co
 (gpf_comm_*). Default swarm: 64 particles on one GPU (config C); 32 per GPU at N > 1, which
 is config D's 256-particle swarm at 8 GPUs (weak scaling, 32 per GPU).
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with a
+Prints ONE JSON line on rank 0 (contract in the task statement). With `--full` it holds a
 "roofline" object for the dominant kernel (k_panel, the MFMA GEMM step) timed
 with HIP events on the library's stream, and a "cpu_baseline" object: the
 CPU oracle (a bit-exact NumPy restatement of the reference's evaluate_loss)
@@ -469,6 +480,11 @@ def main():
                     help="particles per GPU (default 64 on one GPU = config C, 32 per GPU at N > 1 = config D)")
     ap.add_argument("--hetero", action="store_true")
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (the swarm's scores) to DIR/scores.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the profiled pass (roofline, breakdown), the PSO loop, the secondary lines and "
+                         "the CPU baselines; the options below trim those legs")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-profile", action="store_true", help="do not bracket launches with HIP events")
     ap.add_argument("--pso-steps", type=int, default=3, help="secondary: real PSO iterations timed")
@@ -540,6 +556,47 @@ def main():
     fence()
     dt = time.perf_counter() - t0
     xch = (comm.stats()[0] - x0) / args.steps if comm is not None else None  # exchange ms per step, this rank
+    if comm is not None:
+        dt = float(comm.allreduce([dt], op="max")[0])  # max over ranks
+        xch_max = float(comm.allreduce([xch], op="max")[0])
+        xch_min = -float(comm.allreduce([-xch], op="max")[0])
+    evals = P * args.steps                # swarm x iterations, all of them full evaluations
+    value = evals / dt
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: the whole swarm's scores (every rank holds them)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "scores.npy"), np.asarray(sc, dtype=np.float64))
+
+    letter = config_letter(N, d, spg, args.hetero)
+    line = {
+        "metric": f"PSO objective evals/sec (swarm x iters) at N={N} d={d}",
+        "value": value, "unit": "evals/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "dtype": "f64", "data": "synthetic", "full": bool(args.full),
+        "config": {"workload": f"PSO objective, BASELINE config {letter}: synthetic N={N} d={d}, "
+                               f"swarm {spg}/GPU x {world} GPU = {P}",
+                   "N": N, "d": d, "swarm": P, "swarm_per_gpu": spg, "global_batch": P, "seq_len": N,
+                   "parallelism": (f"swarm-shard x{world} (libgpfit {exchange['transport'].upper()} all-reduce)"
+                                   if world > 1 else "single GPU"),
+                   "hetero_noise": bool(args.hetero),
+                   "pso_iters_per_s": args.steps / dt, "particles": "interior l~U[0.05,0.6]^d (full work)"},
+        "build": gpfit.build_info(),
+        "exchange": exchange,
+        # the swarm exchange's own cost (time inside gpf_comm_exchange_scores per step: the
+        # all-reduce of P + G doubles, including the wait for the slowest rank), max and min
+        # over ranks; the min is the collective itself, the max adds the load imbalance
+        "rccl": (exchange["transport"] == "rccl") if exchange else None,
+        "exchange_ms_per_step": xch_max if comm is not None else None,
+        "exchange_ms_per_step_min_rank": xch_min if comm is not None else None,
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if comm is not None:
+            comm.close()
+        ctx.close()
+        return
+
     dt_prof = None
     ctx.reset_profile()
     if not args.no_profile:
@@ -553,14 +610,8 @@ def main():
         dt_prof = time.perf_counter() - t1
     prof = ctx.profile()
     ctx.set_profiling(False)
-    if comm is not None:
-        dt = float(comm.allreduce([dt], op="max")[0])  # max over ranks
-        xch_max = float(comm.allreduce([xch], op="max")[0])
-        xch_min = -float(comm.allreduce([-xch], op="max")[0])
-        if dt_prof is not None:
-            dt_prof = float(comm.allreduce([dt_prof], op="max")[0])
-    evals = P * args.steps                # swarm x iterations, all of them full evaluations
-    value = evals / dt
+    if comm is not None and dt_prof is not None:
+        dt_prof = float(comm.allreduce([dt_prof], op="max")[0])
 
     # secondary: the real PSO update loop (find_len_scales.py:87-141) from a centred LHS;
     # particles clipped onto the box are sentinels (1e13, no GPU work), so its rate is higher
@@ -697,22 +748,10 @@ def main():
         cpu = cpu_baselines(x, y, e, lo, hi, N, d, args.seed)
 
     if rank == 0:
-        letter = config_letter(N, d, spg, args.hetero)
-        line = {
-            "metric": f"PSO objective evals/sec (swarm x iters) at N={N} d={d}",
-            "value": value, "unit": "evals/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        line.update({
             "vs_baseline": (value / cpu["value"]) if cpu else None,
             "vs_baseline_basis": "GPU value / CPU reference-policy baseline (cpu_baseline.value) on this box"
             if cpu else None,
-            "dtype": "f64", "data": "synthetic",
-            "config": {"workload": f"PSO objective, BASELINE config {letter}: synthetic N={N} d={d}, "
-                                   f"swarm {spg}/GPU x {world} GPU = {P}",
-                       "N": N, "d": d, "swarm": P, "swarm_per_gpu": spg, "global_batch": P, "seq_len": N,
-                       "parallelism": (f"swarm-shard x{world} (libgpfit {exchange['transport'].upper()} all-reduce)"
-                                       if world > 1 else "single GPU"),
-                       "hetero_noise": bool(args.hetero),
-                       "pso_iters_per_s": args.steps / dt, "particles": "interior l~U[0.05,0.6]^d (full work)"},
             "configs": secondary,
             "pso_loop": pso,
             "predict": predict,
@@ -724,17 +763,9 @@ def main():
             "gpu_vs_cpu": (value / cpu["value"]) if cpu else None,
             "gpu_vs_cpu_all_cores": (value / cpu["all_cores"]["value"]) if cpu else None,
             "breakdown_ms": breakdown,
-            "build": gpfit.build_info(),
-            "exchange": exchange,
-            # the swarm exchange's own cost (time inside gpf_comm_exchange_scores per step: the
-            # all-reduce of P + G doubles, including the wait for the slowest rank), max and min
-            # over ranks; the min is the collective itself, the max adds the load imbalance
-            "rccl": (exchange["transport"] == "rccl") if exchange else None,
-            "exchange_ms_per_step": xch_max if comm is not None else None,
-            "exchange_ms_per_step_min_rank": xch_min if comm is not None else None,
             "factor_tflops_rank_max": ftf_max if comm is not None else None,
             "factor_tflops_rank_min": ftf_min if comm is not None else None,
-        }
+        })
         print(json.dumps(line), flush=True)
     if comm is not None:
         comm.close()

@@ -7,7 +7,7 @@ timeout -k 10 600 python -u -m pytest tests -x -v -m gpu --timeout 300 --timeout
 rc=$?
 grep -E "passed|failed|error" $O/pytest.log | tail -3
 [ $rc -ne 0 ] && { grep -E "FAILED|Error|assert" $O/pytest.log | head -30; exit $rc; }
-B="python bench.py --steps ${STEPS:-40} --warmup 2 --pso-steps 0 --no-cpu --predict-points 0 --no-hull --no-kmeans --psurf-rows 0 --no-secondary"
+B="python bench.py --full --steps ${STEPS:-40} --warmup 2 --pso-steps 0 --no-cpu --predict-points 0 --no-hull --no-kmeans --psurf-rows 0 --no-secondary"
 for rep in 1 2; do
   for m in "0 1" "1 0" "1 1"; do
     set -- $m

@@ -5,7 +5,7 @@
 cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 O=gpurun_out/${TAG:-r6ev}; mkdir -p $O
-B="python bench.py --steps 3 --warmup 1 --pso-steps 0 --no-cpu --predict-points 0 --no-hull --no-kmeans --psurf-rows 0 --no-secondary"
+B="python bench.py --full --steps 3 --warmup 1 --pso-steps 0 --no-cpu --predict-points 0 --no-hull --no-kmeans --psurf-rows 0 --no-secondary"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof -o bench --output-format csv -- $B > $O/prof.log 2>&1 || exit 4
 f=$(find $O/prof -name "*kernel_trace.csv" | head -1)
 python scripts/kernel_union.py $f 4096 64 3 > $O/kernel_union.txt 2>&1 || true

@@ -7,7 +7,7 @@ rc=$?
 grep -E "passed|failed|error" $O/pytest.log | tail -3
 [ $rc -ne 0 ] && { grep -E "FAILED|Error|assert" $O/pytest.log | head -30; exit $rc; }
 if [ "${BENCH:-0}" = 1 ]; then
-  timeout -k 10 600 python bench.py --steps ${STEPS:-60} > $O/bench.log 2>&1 || { tail -20 $O/bench.log; exit 3; }
+  timeout -k 10 600 python bench.py --full --steps ${STEPS:-60} > $O/bench.log 2>&1 || { tail -20 $O/bench.log; exit 3; }
   python - "$O/bench.log" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
