@@ -6,7 +6,10 @@ the hull grid (gpf_predict). Column naming, file naming, merge semantics and
 messages follow GP_fit.py:20-164.
 
 Optional options.yaml keys (absent = reference behaviour): pso_num_particles (40),
-pso_max_iter (500), pso_max_points (100), pso_seed (none: unseeded global RNG).
+pso_max_iter (500), pso_max_points (100), pso_seed (none: unseeded global RNG);
+len_scale_objective ("calibration": the reference's swarm; "marginal_likelihood": the
+maximum-marginal-likelihood fit, which reuses pso_max_points and pso_seed) and
+mle_num_starts (40).
 """
 from functools import reduce
 from pathlib import Path
@@ -23,7 +26,7 @@ __all__ = ["process_experiment", "write_individual_file", "write_grouped_file", 
            "create_GP"]
 
 _PSO_KEYS = {"pso_num_particles": "num_particles", "pso_max_iter": "max_iter", "pso_max_points": "max_points",
-             "pso_seed": "seed"}
+             "pso_seed": "seed", "len_scale_objective": "objective", "mle_num_starts": "num_starts"}
 
 
 def _pso_overrides(options_path="options.yaml"):

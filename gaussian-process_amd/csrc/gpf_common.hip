@@ -270,18 +270,31 @@ __device__ __forceinline__ void dl_row_offsets(int lane, uint32_t (&o)[4]) {
 // (8 row blocks) x one 16-column slab, so a k-step is 8 A reads, 1 B read and 8 MFMAs.
 // NS: LDS stages (2: double-buffered, the default; 3-4 for one-workgroup-per-CU launches, where
 // the next chunk's transfer has less time behind one chunk of MFMAs than two workgroups give it)
-template <bool NN, bool NEG, int NS = 2, bool BNT = true>
+// TN: A is given transposed, as a [k][r] row panel like the NN B panel: A(r,k) at Ap[k*ldb + r] (both
+// panels share the leading dimension ldb). The f64 16x16x4 A and B fragments are symmetric (lane l:
+// index l & 15, depth l >> 4), so A is staged and read exactly as the NN B side is: one k-row per 1 KiB
+// block, column pair cp of row k in slot cp ^ 8 (k % 4). Row block mi of an operand read then sits in
+// slot group mi ^ (lane >> 4) = (mi & 4) | ((mi & 3) ^ (lane >> 4)): one per-lane offset per mi & 3, the
+// upper row half and the k-step displacements immediates. acc += sum_k A(., k) B(k, .) with nothing
+// transposed in memory (k_lml_grad: W = U^T U from the row-major U).
+template <bool NN, bool NEG, int NS = 2, bool BNT = true, bool TN = false>
 struct DenseRun {
   static_assert(NS >= 2 && NS <= 4, "DenseRun stages");
+  static_assert(!TN || NN, "TN: both operands are [k][c] panels");
   static constexpr int MBR = Geo<128>::MBR;  // 8
   static_assert(Geo<128>::MBC == 1 && Geo<128>::WR == 1, "128-tile wave layout: all rows x one column slab");
-  uint32_t la[4], lb[4];  // LDS read offsets (bytes) per k-step: A rows, B^T rows (!NN) / B (NN, [0] only)
+  uint32_t la[4], lb[4];  // LDS read offsets (bytes) per k-step: A rows (TN: per row block mi & 3), B^T rows (!NN) / B (NN, [0] only)
   uint32_t ga[2], gb[2];  // global byte offsets of the two 1 KiB blocks per operand this wave fills
   int blk0;               // first block index of this wave
 
   __device__ __forceinline__ DenseRun(const Quad<128>& qd, int lda, int ldb, int wave) {
     const int lane = qd.lane, lr = lane & 15, lk = lane >> 4;
-    dl_row_offsets(lane, la);
+    if constexpr (TN) {
+#pragma unroll
+      for (int mi = 0; mi < 4; ++mi) la[mi] = 8u * (uint32_t)(lk * 128 + 2 * (8 * (mi ^ lk) + (lr >> 1)) + (lr & 1));
+    } else {
+      dl_row_offsets(lane, la);
+    }
     if (!NN) {
 #pragma unroll
       for (int s = 0; s < 4; ++s) lb[s] = la[s] + 8u * (uint32_t)(128 * DL_KC + qd.cb * DL_KC);  // dl_sw(cb + lr) = dl_sw(lr)
@@ -294,7 +307,7 @@ struct DenseRun {
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int blk = blk0 + u, row = 8 * blk + (lane >> 3), kp = (lane & 7) ^ dl_sw(row);
-      ga[u] = 8u * (uint32_t)(row * lda + 2 * kp);
+      ga[u] = TN ? 8u * (uint32_t)(blk * ldb + 2 * (lane ^ (8 * (blk & 3)))) : 8u * (uint32_t)(row * lda + 2 * kp);
       gb[u] = NN ? 8u * (uint32_t)(blk * ldb + 2 * (lane ^ (8 * (blk & 3)))) : 8u * (uint32_t)(row * ldb + 2 * kp);
     }
   }
@@ -302,13 +315,13 @@ struct DenseRun {
   template <int BUF>
   __device__ __forceinline__ void issue(const double* Ap, const double* Bp, int ldb, int c, double* smem) const {
     // (uniform_ptr: a no-op where the chunk base is already scalar, as in every dense loop)
-    const char* Ac = uniform_ptr((const char*)(Ap + c * DL_KC));
+    const char* Ac = uniform_ptr(TN ? (const char*)(Ap + (size_t)c * DL_KC * ldb) : (const char*)(Ap + c * DL_KC));
     const char* Bc = uniform_ptr(NN ? (const char*)(Bp + (size_t)c * DL_KC * ldb) : (const char*)(Bp + c * DL_KC));
     double* sbuf = smem + BUF * DL_BUF;
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int blk = blk0 + u;
-      dl_load_s(Ac, ga[u], sbuf + blk * 8 * DL_KC);
+      dl_load_s(Ac, ga[u], sbuf + (TN ? blk * 128 : blk * 8 * DL_KC));
       dl_load_s<BNT && GPF_B_NT != 0>(Bc, gb[u], sbuf + 128 * DL_KC + (NN ? blk * 128 : blk * 8 * DL_KC));
     }
   }
@@ -317,7 +330,10 @@ struct DenseRun {
   template <int M0>
   __device__ __forceinline__ void reads(const char* sb, int s, double (&a)[MBR], double& b) const {
 #pragma unroll
-    for (int mi = M0; mi < MBR; ++mi) a[mi] = *(const double*)(sb + la[s] + mi * 16 * DL_KC * 8);
+    for (int mi = M0; mi < MBR; ++mi) {
+      if constexpr (TN) a[mi] = *(const double*)(sb + la[mi & 3] + (mi >> 2) * 64 * 8 + s * 512 * 8);
+      else a[mi] = *(const double*)(sb + la[s] + mi * 16 * DL_KC * 8);
+    }
     b = NN ? *(const double*)(sb + lb[0] + s * 512 * 8) : *(const double*)(sb + lb[s]);
   }
 
@@ -404,7 +420,8 @@ struct DenseRun {
 // allocation of the dense loop); exactly the MFMAs tri_live admits are issued, so results are
 // bitwise those of per-block skipping. Every wave still passes one barrier per chunk.
 // BNT: the B panel loads non-temporal (a panel read once per launch; GPF_B_NT)
-template <bool NN, bool NEG = false, int TRI = TRI_NONE, int NS = 2, bool BNT = true>
+// TN: A^T given as a [k][r] row panel with B's leading dimension (DenseRun); lda is not used
+template <bool NN, bool NEG = false, int TRI = TRI_NONE, int NS = 2, bool BNT = true, bool TN = false>
 __device__ __forceinline__ void gemm_stream_dl(Acc<128>& acc, const double* __restrict__ Ap, int lda, const double* __restrict__ Bp,
                                int ldb, int K, double* smem, const Quad<128>& qd) {
   const int nch = K / DL_KC;
@@ -412,7 +429,7 @@ __device__ __forceinline__ void gemm_stream_dl(Acc<128>& acc, const double* __re
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const double* Ar = uniform_ptr(Ap);  // scalar bases
   const double* Br = uniform_ptr(Bp);
-  const DenseRun<NN, NEG, NS, BNT> dr(qd, lda, ldb, wave);
+  const DenseRun<NN, NEG, NS, BNT, TN> dr(qd, lda, ldb, wave);
   dr.template issue<0>(Ar, Br, ldb, 0, smem);
   if constexpr (NS >= 3) {  // the first NS-1 chunks in flight
     if (nch > 1) dr.template issue<1>(Ar, Br, ldb, 1, smem);

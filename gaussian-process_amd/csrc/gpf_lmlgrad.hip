@@ -1,0 +1,215 @@
+// gpf_lmlgrad.hip — log marginal likelihood and its length-scale gradient for a batch of
+// particles, from what a factorisation leaves on the device (L, U = L^-1, the szp partials of alpha).
+//
+// Fixed amplitude 1, fixed noise e^2, ARD squared-exponential (GP_func.py:49-65). With
+// Kn = kernel_func(x, x, l) + diag(e^2), W = Kn^-1 = U^T U and alpha = W y:
+//   LML       = -1/2 y^T alpha - sum_i log L_ii - N/2 log(2 pi)
+//   dLML/dl_k = sum_{i>j} (alpha_i alpha_j - W_ij) K_ij (x_ik - x_jk)^2 / l_k^3
+// (K_ij the noise-free kernel value; the diagonal terms vanish and the noise does not depend on l,
+// so only the strict lower triangle is needed). W is never stored: every 128x128 tile of it is
+// reduced in registers, as k_predict_vsq reduces V.
+#pragma once
+#include "gpf_common.hip"
+
+namespace gpf {
+
+// LDS of k_lml_grad: the GEMM's two stages, reused by the epilogue for the tile's coordinates
+// ([d][T] rows | [d][T] columns, d <= DMAX: exactly DL_STAGE at d = 32), then the squared norms and
+// alpha of the rows and columns, then the waves' partial sums.
+constexpr int LG_VEC = DL_STAGE;           // n_i | n_j | alpha_i | alpha_j, T each
+constexpr int LG_RED = LG_VEC + 4 * T;     // [8 waves][DMAX]
+constexpr int LG_LDS = LG_RED + 8 * DMAX;  // doubles (69.6 KiB: two workgroups per CU)
+static_assert(2 * DMAX * T <= DL_STAGE, "k_lml_grad: the tile's coordinates fit the GEMM stages");
+
+// Lower tile (I, J <= I) of W = U^T U for particle blockIdx.y, reduced against the kernel derivative:
+//   W_IJ = sum_{K >= I} U_KI^T U_KJ, depth (nt - I) 128. Both operands are [k][c] panels of the
+//   row-major U (the TN flavour of the streaming core: nothing is transposed in memory). Tiles K < I
+//   hold zeros (U is lower triangular) and the tiles above the diagonal of d_U are scratch: neither
+//   is read. U's diagonal blocks carry zeros above their diagonal (factor128) and the padded rows are
+//   identity rows (k_build_cov pads K with an identity block), so the padding adds exact zeros to
+//   every W_ij with i, j < N. On the diagonal tiles only the lower triangle is formed (TRI_C_LOWER).
+// Epilogue, per element j < i < N: K_ij recomputed from x and l with k_build_cov's operation order
+// (d_L holds L by now), w = (alpha_i alpha_j - W_ij) K_ij, then per coordinate k
+//   partial[p][tile][k] = sum_ij w_ij (x_ik - x_jk)^2
+// summed in a fixed order: per lane over its 32 rows (ascending), over the 4 lane groups
+// (sum_lane_groups), over the wave's 16 columns (xor 8, 4, 2, 1), over the 8 waves in wave order. No
+// floating-point atomics: the same inputs give the same bits.
+// Tile index blockIdx.x = I (I + 1) / 2 + J: ascending I, so the deepest tiles are dispatched first.
+// grid: (nt (nt + 1) / 2, particles)
+__global__ __launch_bounds__(Geo<T>::NTH, 4) void k_lml_grad(int N, int Npad, int nt, int d,
+                                                             const double* __restrict__ x,
+                                                             const double* __restrict__ ls,
+                                                             const double* __restrict__ U,
+                                                             const double* __restrict__ alpha,
+                                                             double* __restrict__ partial) {
+  __shared__ __attribute__((aligned(16))) double smem[LG_LDS];
+  const int idx = blockIdx.x, p = blockIdx.y;
+  int I = (int)((sqrt(8.0 * idx + 1.0) - 1.0) * 0.5);
+  while ((I + 1) * (I + 2) / 2 <= idx) ++I;
+  while (I * (I + 1) / 2 > idx) --I;
+  const int J = idx - I * (I + 1) / 2;
+  const Quad<T> qd;
+  Acc<T> acc;
+  acc.zero();
+  {
+    const double* Up = U + (size_t)p * Npad * Npad + (size_t)I * T * Npad;  // block row I: the first K
+    const int depth = (nt - I) * T;
+    // (both panels are re-read by other tiles of the launch: default cache policy)
+    if (I == J)
+      gemm_stream_dl<true, false, TRI_C_LOWER, 2, false, true>(acc, Up + (size_t)I * T, Npad, Up + (size_t)J * T, Npad,
+                                                               depth, smem, qd);
+    else
+      gemm_stream_dl<true, false, TRI_NONE, 2, false, true>(acc, Up + (size_t)I * T, Npad, Up + (size_t)J * T, Npad,
+                                                            depth, smem, qd);
+  }
+  // (the GEMM ends with a barrier: the stages are free)
+  const int tid = threadIdx.x;
+  const double* lp = ls + (size_t)p * d;
+  double* sa = smem;          // [d][T] rows (block I): scaled coordinates, then the raw ones
+  double* sb = smem + d * T;  // [d][T] columns (block J)
+  double* na = smem + LG_VEC;
+  double* nb = na + T;
+  double* ali = nb + T;
+  double* alj = ali + T;
+  double* red = smem + LG_RED;
+  if (tid < 2 * T) {  // as cov_tile_acc: a = x / l, |a|^2 summed over the coordinates in order
+    const int t = tid & (T - 1);
+    const bool rows = tid < T;
+    const int g = (rows ? I : J) * T + t;
+    double* a = rows ? sa : sb;
+    double nrm = 0.0;
+    if (g < N) {
+      for (int k = 0; k < d; ++k) {
+        const double v = x[(size_t)k * N + g] / lp[k];
+        a[k * T + t] = v;
+        nrm = nrm + v * v;
+      }
+    } else {
+      for (int k = 0; k < d; ++k) a[k * T + t] = 0.0;  // (padding: finite, masked below)
+    }
+    (rows ? na : nb)[t] = nrm;
+    (rows ? ali : alj)[t] = g < N ? alpha[(size_t)p * Npad + g] : 0.0;
+  }
+  __syncthreads();
+  static_assert(Acc<T>::MBC == 1, "one column per lane");
+  constexpr int MBR = Acc<T>::MBR;
+  const int col = qd.col(0), gj = J * T + col;
+  {
+    const double nc = nb[col], aj = alj[col], b0 = sb[col];
+#pragma unroll
+    for (int mi = 0; mi < MBR; ++mi) {
+      double dot[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) dot[r] = sa[qd.row(mi, r)] * b0;
+      for (int k = 1; k < d; ++k) {
+        const double bk = sb[k * T + col];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) dot[r] = fma(sa[k * T + qd.row(mi, r)], bk, dot[r]);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = qd.row(mi, r), gi = I * T + row;
+        double r2 = (na[row] + nc) - 2.0 * dot[r];
+        r2 = r2 > 0.0 ? r2 : 0.0;  // np.maximum(sq_dist, 0)
+        const double w = (ali[row] * aj - acc.v[mi][0][r]) * exp(-0.5 * r2);
+        double wm = (gj < gi && gi < N) ? w : 0.0;
+        // (formed here: left to the optimiser, the 32 exponentials sink past the barriers below into the
+        // coordinate loop's preheader, and their 32 arguments spill on the way)
+        asm volatile("" : "+v"(wm));
+        acc.v[mi][0][r] = wm;
+        __builtin_amdgcn_sched_barrier(0);  // (one exp at a time, as cov_tile_acc)
+      }
+    }
+  }
+  __syncthreads();
+  if (tid < 2 * T) {  // the raw coordinates replace the scaled ones
+    const int t = tid & (T - 1);
+    const bool rows = tid < T;
+    const int g = (rows ? I : J) * T + t;
+    double* a = rows ? sa : sb;
+    for (int k = 0; k < d; ++k) a[k * T + t] = g < N ? x[(size_t)k * N + g] : 0.0;
+  }
+  __syncthreads();
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  for (int k = 0; k < d; ++k) {
+    const double bk = sb[k * T + col];
+    double s = 0.0;
+#pragma unroll
+    for (int mi = 0; mi < MBR; ++mi) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const double df = sa[k * T + qd.row(mi, r)] - bk;
+        s = fma(acc.v[mi][0][r], df * df, s);
+      }
+      __builtin_amdgcn_sched_barrier(0);  // (the row reads in groups of 4: not all 32 in flight)
+    }
+    s = sum_lane_groups(s);
+    s = s + __shfl_xor(s, 8);
+    s = s + __shfl_xor(s, 4);
+    s = s + __shfl_xor(s, 2);
+    s = s + __shfl_xor(s, 1);
+    if (qd.lane == 0) red[wave * DMAX + k] = s;
+  }
+  __syncthreads();
+  if (tid < d) {
+    double s = red[tid];
+#pragma unroll
+    for (int w = 1; w < 8; ++w) s = s + red[w * DMAX + tid];
+    partial[((size_t)p * gridDim.x + idx) * d + tid] = s;
+  }
+}
+
+// alpha_c = sum_t szp[p][t][c] over row tiles t >= c / 128, for every particle of the chunk
+// (k_alpha: slot 0 only). alpha: [particles][Npad]. grid: (ceil(N/256), particles)
+__global__ __launch_bounds__(NTHR) void k_alpha_batch(int N, int Npad, int nt, const double* __restrict__ szp,
+                                                      double* __restrict__ alpha) {
+  const int c = blockIdx.x * NTHR + threadIdx.x, p = blockIdx.y;
+  if (c >= N) return;
+  const double* sp = szp + (size_t)p * nt * Npad;
+  double a = 0.0;
+  for (int t = c / T; t < nt; ++t) a = a + sp[(size_t)t * Npad + c];
+  alpha[(size_t)p * Npad + c] = a;
+}
+
+// lml[p] = -1/2 y^T alpha - sum_i log L_ii - N/2 log(2 pi). Thread t sums the points t, t + 256, ..
+// in order; the 256 thread sums then fold in a fixed tree. grid: (particles)
+__global__ __launch_bounds__(NTHR) void k_lml_value(int N, int Npad, const double* __restrict__ y,
+                                                    const double* __restrict__ alpha, const double* __restrict__ L,
+                                                    double* __restrict__ lml) {
+  __shared__ double sy[NTHR], sl[NTHR];
+  const int tid = threadIdx.x, p = blockIdx.x;
+  const double* ap = alpha + (size_t)p * Npad;
+  const double* Lp = L + (size_t)p * Npad * Npad;
+  double ya = 0.0, ld = 0.0;
+  for (int i = tid; i < N; i += NTHR) {
+    ya = fma(y[i], ap[i], ya);
+    ld = ld + log(Lp[(size_t)i * (Npad + 1)]);
+  }
+  sy[tid] = ya;
+  sl[tid] = ld;
+  __syncthreads();
+  for (int h = NTHR / 2; h > 0; h >>= 1) {
+    if (tid < h) {
+      sy[tid] = sy[tid] + sy[tid + h];
+      sl[tid] = sl[tid] + sl[tid + h];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) lml[p] = (-0.5 * sy[0] - sl[0]) - 0.5 * (double)N * 1.8378770664093453;  // log(2 pi)
+}
+
+// grad[p][k] = (sum over the tiles, in tile order, of partial[p][tile][k]) / l_k^3.
+// grid: (particles), DMAX threads
+__global__ __launch_bounds__(DMAX) void k_lml_grad_sum(int ntile, int d, const double* __restrict__ partial,
+                                                       const double* __restrict__ ls, double* __restrict__ grad) {
+  const int k = threadIdx.x, p = blockIdx.x;
+  if (k >= d) return;
+  const double* pp = partial + (size_t)p * ntile * d + k;
+  double s = 0.0;
+  for (int t = 0; t < ntile; ++t) s = s + pp[(size_t)t * d];
+  const double l = ls[(size_t)p * d + k];
+  grad[(size_t)p * d + k] = s / (l * l * l);
+}
+
+}  // namespace gpf

@@ -25,6 +25,7 @@
 #include "gpf_persist.hip"
 #include "gpf_objective.hip"
 #include "gpf_predict.hip"
+#include "gpf_lmlgrad.hip"
 #include "gpf_probsurf.hip"
 #include "gpf_hull.hip"
 #include "gpf_kmeans.hip"
@@ -114,6 +115,11 @@ struct gpf_ctx {
   int64_t s_rows = 0;
   int s_e = 0;
   int* d_hist = nullptr;
+  // gpf_lml_batch: per-tile gradient partials [particles][tiles][d] and the gradient rows behind them,
+  // grow-only and outside the chunk workspace (bytes_per_particle): the evaluation path's chunk
+  // capacity does not depend on it
+  double* g_part = nullptr;
+  size_t g_cap = 0;
   // pinned host staging for the per-batch transfers (async DMA, capturable in graphs)
   double* h_ls = nullptr;
   double* h_loss = nullptr;
@@ -952,6 +958,7 @@ void gpf_close(gpf_ctx* c) {
   free_work(c);
   hipFree(c->d_x); hipFree(c->d_y); hipFree(c->d_e);
   hipFree(c->d_clk);
+  hipFree(c->g_part);
   hipFree(c->d_sig); hipFree(c->d_exp); hipFree(c->d_lo); hipFree(c->d_hi);
   hipFree(c->km_x); hipFree(c->km_c); hipFree(c->km_dist); hipFree(c->km_sums); hipFree(c->km_cnt); hipFree(c->km_lab);
   for (auto e : c->pool) hipEventDestroy(e);
@@ -1423,6 +1430,90 @@ int gpf_log_marginal_likelihood(gpf_ctx* c, const double* ls, double* out) {
   for (int64_t i = 0; i < N; ++i) ld += std::log(dg[i]);
   *out = -0.5 * ya - ld - 0.5 * (double)N * std::log(2.0 * M_PI);
   return GPF_OK;
+}
+
+int gpf_lml_batch(gpf_ctx* c, const double* ls, int P, double* lml, double* grad, int* status, int* bad_idx) {
+  if (!c) return GPF_BAD_ARG;
+  if (bad_idx) *bad_idx = -1;
+  if (P < 0 || (P > 0 && (!ls || !lml))) return bad_arg(c, "gpf_lml_batch: bad arguments");
+  if (c->N <= 0) return bad_arg(c, "gpf_lml_batch: call gpf_set_data first");
+  const int d = c->d, nt = c->nt;
+  for (size_t i = 0; i < (size_t)P * d; ++i)
+    if (!(ls[i] > 0.0) || !std::isfinite(ls[i])) return bad_arg(c, "gpf_lml_batch: length scales must be finite and > 0");
+  if (P == 0) return GPF_OK;
+  hipSetDevice(c->device);
+  const int64_t N = c->N, Np = c->Npad;
+  int rc = ensure_work(c, P);
+  if (rc) return rc;
+  const int cap = c->cap;
+  const int ntile = nt * (nt + 1) / 2;
+  double* d_grad = nullptr;
+  if (grad) {
+    const int pcm = std::min(cap, P);
+    const size_t need = ((size_t)pcm * ntile * d + (size_t)pcm * d) * 8;
+    if (need > c->g_cap) {
+      GPF_HIP(c, hipStreamSynchronize(c->stream));
+      hipFree(c->g_part);
+      c->g_part = nullptr;
+      c->g_cap = 0;
+      GPF_HIP(c, hipMalloc(&c->g_part, need));
+      c->g_cap = need;
+    }
+    d_grad = c->g_part + (size_t)pcm * ntile * d;
+  }
+  std::vector<double> hg;
+  if (grad) hg.resize((size_t)std::min(cap, P) * d);
+  int ret = GPF_OK;
+  for (int s = 0; s < P; s += cap) {
+    const int pc = std::min(cap, P - s);
+    std::memcpy(c->h_ls, ls + (size_t)s * d, (size_t)pc * d * 8);
+    GPF_HIP(c, hipMemcpyAsync(c->d_ls, c->h_ls, (size_t)pc * d * 8, hipMemcpyHostToDevice, c->stream));
+    rc = run_factor(c, pc);
+    if (rc) return rc;
+    // alpha into the mu slots, the value into the loss slots of the chunk workspace
+    rc = launch(c, PC_LOSS, 0.0, [&] {
+      hipLaunchKernelGGL(gpf::k_alpha_batch, dim3((unsigned)((N + NTHR - 1) / NTHR), pc), dim3(NTHR), 0, c->stream, (int)N,
+                         (int)Np, nt, c->d_szp, c->d_mu);
+      hipLaunchKernelGGL(gpf::k_lml_value, dim3(pc), dim3(NTHR), 0, c->stream, (int)N, (int)Np, c->d_y, c->d_mu, c->d_L,
+                         c->d_loss);
+    });
+    if (rc) return rc;
+    if (grad) {
+      // the same N^3/3 flops as the factorisation: sum over the lower tiles (I, J) of 2 T^3 (nt - I)
+      double fl = 0.0;
+      for (int I = 0; I < nt; ++I) fl += 2.0 * (double)T * T * T * (double)(nt - I) * (I + 1);
+      rc = launch(c, PC_LOSS, fl * pc, [&] {
+        hipLaunchKernelGGL(gpf::k_lml_grad, dim3((unsigned)ntile, pc), dim3(gpf::Geo<T>::NTH), 0, c->stream, (int)N,
+                           (int)Np, nt, d, c->d_x, c->d_ls, c->d_U, c->d_mu, c->g_part);
+        hipLaunchKernelGGL(gpf::k_lml_grad_sum, dim3(pc), dim3(gpf::DMAX), 0, c->stream, ntile, d, c->g_part, c->d_ls,
+                           d_grad);
+      });
+      if (rc) return rc;
+      GPF_HIP(c, hipMemcpyAsync(hg.data(), d_grad, (size_t)pc * d * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    GPF_HIP(c, hipMemcpyAsync(c->h_loss, c->d_loss, (size_t)pc * 8, hipMemcpyDeviceToHost, c->stream));
+    GPF_HIP(c, hipMemcpyAsync(c->h_info, c->d_info, (size_t)pc * 4, hipMemcpyDeviceToHost, c->stream));
+    GPF_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->prof) harvest(c);
+    for (int q = 0; q < pc; ++q) {
+      const int p = s + q;
+      if (c->h_info[q] & 2) {
+        c->err = "k_step: diagonal-block hand-off timed out";
+        return GPF_HIP_ERROR;
+      }
+      const bool bad = c->h_info[q] != 0;
+      if (bad && ret == GPF_OK) {
+        ret = GPF_NOT_PD;
+        if (bad_idx) *bad_idx = p;
+        c->err = "Matrix is not positive definite";
+      }
+      if (status) status[p] = bad ? GPF_NOT_PD : GPF_OK;
+      lml[p] = bad ? -INFINITY : c->h_loss[q];
+      if (grad)
+        for (int k = 0; k < d; ++k) grad[(size_t)p * d + k] = bad ? NAN : hg[(size_t)q * d + k];
+    }
+  }
+  return ret;
 }
 
 static int plan_fail(char* msg, int len, const char* fmt, ...) {

@@ -13,6 +13,11 @@ len_scale_opt keeps the reference defaults (40 particles, 500 iterations,
 KMeans subsample above 100 points) and adds keyword-only overrides used by the
 benchmarks and the tests: num_particles, max_iter, max_points,
 init_positions, seed.
+
+objective="marginal_likelihood" replaces the swarm by a maximum-marginal-likelihood
+fit (gpfit.mle.fit_lml: batched starts, then L-BFGS-B with the gradient from
+gpf_lml_batch); it takes num_starts, max_points and seed. The default,
+objective="calibration", is the reference's search.
 """
 import numpy as np
 
@@ -24,8 +29,17 @@ __all__ = ["len_scale_opt", "wass_loss", "evaluate_loss", "evaluate_loss_helper"
 
 
 def len_scale_opt(x_known, y_known, e_known, PSO_progress, *, num_particles=40, max_iter=500,
-                  max_points=100, init_positions=None, seed=None):
-    """PSO search for the per-dimension length scales (find_len_scales.py:22-150)."""
+                  max_points=100, init_positions=None, seed=None, objective="calibration", num_starts=40):
+    """PSO search for the per-dimension length scales (find_len_scales.py:22-150), or with
+    objective="marginal_likelihood" the maximum-marginal-likelihood fit (gpfit.mle.fit_lml)."""
+    if objective == "marginal_likelihood":
+        from gpfit.mle import fit_lml
+        best, _ = fit_lml(np.asarray(x_known, dtype=np.float64), np.asarray(y_known, dtype=np.float64),
+                          np.asarray(e_known, dtype=np.float64), num_starts=num_starts, max_points=max_points,
+                          seed=seed, verbose=bool(PSO_progress))
+        return best
+    if objective != "calibration":
+        raise ValueError(f"len_scale_opt: unknown objective {objective!r} (calibration or marginal_likelihood)")
     best, _ = particle_swarm(np.asarray(x_known, dtype=np.float64), np.asarray(y_known, dtype=np.float64),
                              np.asarray(e_known, dtype=np.float64), PSO_progress,
                              num_particles=num_particles, max_iter=max_iter, max_points=max_points,

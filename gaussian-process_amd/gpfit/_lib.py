@@ -38,6 +38,7 @@ SIGNATURES = {
     "gpf_predict": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int64, ctypes.c_int64, _dp, _dp]),
     "gpf_kernel": (ctypes.c_int, [_vp, _dp, ctypes.c_int64, _dp, ctypes.c_int64, ctypes.c_int, _dp, _dp]),
     "gpf_log_marginal_likelihood": (ctypes.c_int, [_vp, _dp, _dp]),
+    "gpf_lml_batch": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _dp, _dp, _ip, _ip]),
     "gpf_set_profiling": (ctypes.c_int, [_vp, ctypes.c_int]),
     "gpf_get_profile": (ctypes.c_int, [_vp, _dp, ctypes.c_int]),
     "gpf_reset_profile": (ctypes.c_int, [_vp]),
@@ -258,6 +259,28 @@ class Context:
         self._check(self.lib.gpf_log_marginal_likelihood(self._h, _ptr(ls), ctypes.byref(out)),
                     "gpf_log_marginal_likelihood")
         return out.value
+
+    def lml_batch(self, positions, grad=True, strict=True):
+        """Log marginal likelihood of every row of positions (P, d) and, with grad, its gradient
+        in the length scales (gpf_lml_batch): (lml (P,), grad (P, d) or None). Needs set_data
+        only. A particle whose covariance is not positive definite raises LinAlgError with
+        .particle set to its row (strict), or gets lml = -inf and a NaN gradient row while the
+        other rows are computed (strict=False)."""
+        P = _f64(positions)
+        if P.ndim == 1:
+            P = P.reshape(1, -1)
+        n = P.shape[0]
+        if self.d and P.shape[1] != self.d:
+            raise ValueError(f"positions must be (P, {self.d})")
+        lml = np.empty(n)
+        g = np.empty((n, P.shape[1])) if grad else None
+        status = np.zeros(n, dtype=np.int32)
+        bad = ctypes.c_int(-1)
+        rc = self.lib.gpf_lml_batch(self._h, _ptr(P), n, _ptr(lml), _ptr(g) if grad else None,
+                                    status.ctypes.data_as(_ip), ctypes.byref(bad))
+        if rc != GPF_NOT_PD or strict:
+            self._check(rc, "gpf_lml_batch", bad)
+        return lml, g
 
     # -- measurement hooks --
     def set_profiling(self, on=True):

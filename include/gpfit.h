@@ -93,6 +93,25 @@ int gpf_kernel(gpf_ctx* ctx, const double* x1_dN1, int64_t N1,
  * none): -1/2 y^T alpha - sum log L_ii - N/2 log(2 pi). */
 int gpf_log_marginal_likelihood(gpf_ctx* ctx, const double* ls, double* out);
 
+/* Batched log marginal likelihood and its gradient in the length scales (fixed amplitude 1,
+ * fixed noise e^2, ARD squared-exponential), the objective of a maximum-marginal-likelihood fit
+ * (gpfit.mle.fit_lml). ls_Pd is (P, d) row-major. Needs gpf_set_data only (no grid, no box).
+ *   lml_P[p]     = -1/2 y^T alpha - sum log L_ii - N/2 log(2 pi)
+ *   grad_Pd[p,k] = dLML/dl_k = sum_{i>j} (alpha_i alpha_j - W_ij) K_ij (x_ik - x_jk)^2 / l_k^3,
+ *                  W = Kn^-1, K the noise-free kernel (nullable: without it the gradient pass
+ *                  is not run)
+ *   status_P[p]  = GPF_OK or GPF_NOT_PD (nullable)
+ * Everything is computed on the device from the factorisation's L, U = L^-1 and alpha; the
+ * particles are chunked as in gpf_eval_batch. A particle whose covariance is not positive
+ * definite gets lml = -inf and a NaN gradient row and does not spoil the others: every other
+ * output is written, then the call returns GPF_NOT_PD with *bad_idx the first such particle.
+ * GPF_BAD_ARG, before any device work, if P < 0 or any length scale is not finite and > 0.
+ * Repeating a call on the same context and data gives the same bits (fixed-order sums, no
+ * floating-point atomics); results may differ in the last bits between batch sizes, as the
+ * factorisation's schedule depends on the batch. */
+int gpf_lml_batch(gpf_ctx* ctx, const double* ls_Pd, int P, double* lml_P, double* grad_Pd,
+                  int* status_P, int* bad_idx);
+
 /* Probability surface of merged GP results (replaces calc_prob_surf.py:15-30,67-81; SURVEY.md
  * §8f row 4). tails: M rows x E entries (row-major) = each merged-frame row after its kinematic
  * columns, non-finite = missing. Per row: y[100] (the numpy.linspace grid), p[100] (bin
