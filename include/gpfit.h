@@ -229,9 +229,9 @@ int gpf_tile(void);
 const char* gpf_build_info(void);
 
 /* Host-only structural check of the k_step dispatch plan (needs no device and no context):
- * for a chunk of pc particles with nt block columns, under the current GPF_GROUPS /
- * GPF_SPLIT_K / GPF_STEP_GROUP environment, builds the
- * launch list run_factor issues and decodes every workgroup of every launch with the kernel's
+ * for a chunk of pc particles with nt block columns, under the current GPF_* tuning environment
+ * (read once per call), builds the plan run_factor walks (plan_factor, csrc/gpf_plan.hip: the same
+ * object, not a second derivation) and decodes every workgroup of every launch with the kernel's
  * own decoder (gpf::step_decode). Checks that every (block column, particle, tile) is computed
  * exactly once (one whole-tile workgroup, or all S depth pieces exactly once, whose S arrivals
  * on a zeroed counter elect exactly one finisher), that pieces stay inside the split-K buffers,
@@ -250,6 +250,9 @@ const char* gpf_build_info(void);
  * exists (the tile's 8 or 16 ids behind, on the same XCD), and the partial SYRK of block J+2; it is
  * followed on its stream by the follow launch J+1, whose tiles read those partials (slots inside
  * the group's buffer).
+ * Look-ahead pieces (GPF_LA_ALL; gpf::lall_decode): every piece of a producing launch once, inside
+ * the piece buffer, consumed by the next launch of its group, under a tag that carries the group's
+ * particle count whole (groups of more than 4095 particles plan without the pieces).
  * stats (nullable, 11 entries): launches, workgroups (persistent: items), whole tiles, split
  * tiles, S (all-tile split factor), largest split factor, particle groups, diagonal
  * workgroups, SYRK workgroups (items), persistent (0/1), lead launches of paired block columns. Returns GPF_OK, or

@@ -473,6 +473,59 @@ def test_all_tile_lookahead_pieces(ctx, monkeypatch, N, d, P, pb, first, frm):
     assert _rel(gm[0], mo) < RTOL_MU_SD and _rel(gs[0], so) < RTOL_MU_SD
 
 
+def test_scratch_buffers_across_schedules_on_one_context(monkeypatch):
+    """Every scratch buffer of the factorisation (Scratch::grow, sized by plan_factor) on one live
+    context, across grow / reuse / a larger chunk, at the smallest shape that uses them all (nt = 4:
+    the floor of pairs, pieces and the split): the paired columns' partials and start words at 8 then
+    16 particles (regrown, the start words re-zeroed on the stream), the piece buffer (its knobs set on
+    top of the first steps', which keep the launches unsplit) and, with the pieces from launch 2 on, the
+    critical-tile look-ahead buffer that feeds that launch, the split buffers of a single particle, then
+    8 particles again. Each step's losses are bitwise those of the same call on a fresh context."""
+    import gpfit
+    N, d = 512, 2
+    rng = np.random.default_rng(512)
+    x = rng.uniform(size=(d, N))
+    y = np.sum(np.sin(2 * np.pi * x), axis=0) + 0.1 * rng.standard_normal(N)
+    e = rng.uniform(0.05, 0.2, size=N)
+    s, ex = ref_cpu.sigma_grid()
+    lo, hi = ref_cpu.search_bounds(x)
+    Q = rng.uniform(0.1, 0.5, size=(16, d))
+    pairs = {"GPF_PERSIST": "0", "GPF_EARLY_DIAG": "0", "GPF_SPLIT_K": "1", "GPF_PAIR": "1"}
+    pieces = dict(pairs, GPF_EARLY_DIAG="1", GPF_LA_ALL="1", GPF_LA_ALL_FROM="1")
+    pieces2 = dict(pieces, GPF_LA_ALL_FROM="2")
+    steps = [(8, pairs), (16, pairs), (16, pieces), (16, pieces2), (1, {}), (8, {})]
+    knobs = sorted(pieces)
+
+    def fresh():
+        c = gpfit.Context(0)
+        c.set_data(x, y, e)
+        c.set_grid(s, ex, lo, hi)
+        return c
+
+    live = fresh()
+    try:
+        for i, (P, kv) in enumerate(steps):
+            for k in knobs:
+                monkeypatch.delenv(k, raising=False)
+            for k, v in kv.items():
+                monkeypatch.setenv(k, v)
+            st = gpfit.plan_check(P, 4)
+            assert (st["lead_launches"] > 0) == (kv is pairs) and (st["split_tiles"] > 0) == (not kv), (i, st)
+            if kv in (pieces, pieces2):  # unsplit early-diagonal launches with piece workgroups beside the tiles
+                assert st["diag_workgroups"] == 4 * P and st["split_tiles"] == 0, (i, st)
+                assert st["workgroups"] > st["whole_tiles"] + st["diag_workgroups"] + st["syrk_workgroups"], (i, st)
+            got = live.eval_batch(Q[:P])
+            ref = fresh()
+            try:
+                want = ref.eval_batch(Q[:P])
+            finally:
+                ref.close()
+            np.testing.assert_array_equal(got, want, err_msg=f"step {i}: {P} particles, {kv}")
+            assert np.all(np.isfinite(got)) and np.all(got < 1e13)
+    finally:
+        live.close()
+
+
 def test_sentinels_never_reach_gpu_and_mix_with_live_particles(ctx, f2):
     x, y, e = f2["c0_x"], f2["c0_y"], f2["c0_e"]
     lo, hi = f2["c0_lo"], f2["c0_hi"]

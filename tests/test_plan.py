@@ -1,7 +1,7 @@
 """Host-side enumeration of the k_step dispatch plan (no GPU needed).
 
-gpf_plan_check (include/gpfit.h) builds the launch list run_factor issues (num_groups,
-split_k, step_group and the grid sizing in csrc/gpfit_api.hip) and decodes every
+gpf_plan_check (include/gpfit.h) checks the plan run_factor walks (plan_factor with num_groups,
+split_k, step_group and the grid sizing in csrc/gpf_plan.hip) and decodes every
 workgroup of every launch with the kernel's own decoder (gpf::step_decode). Every
 (block column, particle, tile) must be computed exactly once: one whole-tile workgroup, or
 all S depth pieces exactly once (the flat finish's counters of that tile);
