@@ -13,7 +13,7 @@ import numpy as np
 
 from gpfit._lib import default_context
 
-__all__ = ["GP", "kernel_func"]
+__all__ = ["GP", "GP_cov", "GP_draws", "kernel_func"]
 
 
 def GP(x_known, y_known, e_known, x_fit, lengths, batch_size=10000):
@@ -33,6 +33,30 @@ def GP(x_known, y_known, e_known, x_fit, lengths, batch_size=10000):
     ctx = default_context()
     ctx.set_data(x_known, y_known, e_known)
     return ctx.predict(lengths, x_fit, batch_size)
+
+
+def GP_cov(x_known, y_known, e_known, x_fit, lengths):
+    """Joint latent posterior at x_fit (d, M): (mu (M,), cov (M, M)).
+
+    mu is GP()'s mean bit for bit; cov = K_ss - K_s^T Kn^-1 K_s is dense, exactly symmetric and
+    not clipped on its diagonal (GP()'s sigma is sqrt(clip(diag(cov), 1e-12))). The reference has
+    no counterpart: GP_func.py:39 keeps the diagonal only. All M points go in one call: cov and
+    the two N x M matrices behind it must fit the device (ValueError names the largest M).
+    """
+    x_known = np.asarray(x_known, dtype=np.float64)
+    x_fit = np.asarray(x_fit, dtype=np.float64)
+    if x_fit.ndim != 2 or x_fit.shape[0] != x_known.shape[0]:
+        raise ValueError("x_fit must be (d, M) with the same d as x_known")
+    ctx = default_context()
+    ctx.set_data(x_known, y_known, e_known)
+    return ctx.predict_cov(lengths, x_fit)
+
+
+def GP_draws(x_known, y_known, e_known, x_fit, lengths, n_draws, seed=None):
+    """n_draws joint draws of the latent GP at x_fit: (n_draws, M), from N(GP_cov's mu, cov) by a
+    host Cholesky factor of cov + jitter I (gpfit.posterior.draws_from; default_rng(seed))."""
+    from gpfit.posterior import sample_posterior
+    return sample_posterior(x_known, y_known, e_known, x_fit, lengths, n_draws, seed=seed)[0]
 
 
 def kernel_func(x1, x2, l):

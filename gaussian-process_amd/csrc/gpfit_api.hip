@@ -25,6 +25,7 @@
 #include "gpf_persist.hip"
 #include "gpf_objective.hip"
 #include "gpf_predict.hip"
+#include "gpf_postcov.hip"
 #include "gpf_lmlgrad.hip"
 #include "gpf_probsurf.hip"
 #include "gpf_hull.hip"
@@ -120,6 +121,14 @@ struct gpf_ctx {
   double* p_vz = nullptr;                      // per row tile of V = U K_s: V^T z partials of mu (gpf::k_predict_vsq)
   int64_t p_cols = 0, p_np = 0;
   int p_d = 0, p_nt = 0;
+  // gpf_predict_cov's buffers, apart from gpf_predict's (either call leaves the other's alone) and
+  // kept between calls under the same rule: the query coordinates, K_s and V (c_np x c_cols each),
+  // Sigma (c_cols x c_cols), the vsq / vz partials, (mu | sd), and pinned staging for the
+  // coordinates and the mean
+  double *c_xf = nullptr, *c_ks = nullptr, *c_v = nullptr, *c_cov = nullptr, *c_vsq = nullptr, *c_vz = nullptr;
+  double *c_mu = nullptr, *c_hx = nullptr, *c_hmu = nullptr;
+  int64_t c_cols = 0, c_np = 0;
+  int c_d = 0, c_nt = 0;
   // gpf_prob_surface's row-chunk buffers, kept between calls like the prediction's
   double *s_t = nullptr, *s_cmp = nullptr, *s_y = nullptr, *s_p = nullptr;
   double4* s_info = nullptr;
@@ -238,7 +247,18 @@ int Scratch::grow(gpf_ctx* c, size_t bytes, bool zero, bool sync) {
   return GPF_OK;
 }
 
+static void free_pcov(gpf_ctx* c) {
+  hipFree(c->c_xf); hipFree(c->c_ks); hipFree(c->c_v); hipFree(c->c_cov); hipFree(c->c_vsq); hipFree(c->c_vz);
+  hipFree(c->c_mu);
+  hipHostFree(c->c_hx); hipHostFree(c->c_hmu);
+  c->c_xf = c->c_ks = c->c_v = c->c_cov = c->c_vsq = c->c_vz = c->c_mu = nullptr;
+  c->c_hx = c->c_hmu = nullptr;
+  c->c_cols = c->c_np = 0;
+  c->c_d = c->c_nt = 0;
+}
+
 static void free_pred(gpf_ctx* c) {
+  free_pcov(c);
   hipFree(c->p_xf); hipFree(c->p_ks); hipFree(c->p_vsq); hipFree(c->p_mu); hipFree(c->p_sd); hipFree(c->p_vz);
   hipHostFree(c->p_hx); hipHostFree(c->p_hout);
   c->p_xf = c->p_ks = c->p_vsq = c->p_mu = c->p_sd = c->p_vz = nullptr;
@@ -938,6 +958,127 @@ int gpf_predict(gpf_ctx* c, const double* ls, const double* xfit, int64_t M, int
   // keep the query-chunk buffers for the next call only while they are modest (a huge batch_size
   // can size them up to half of free HBM; see keep_bytes)
   if ((double)c->p_np * (double)c->p_cols * 8.0 > keep_bytes(knobs)) free_pred(c);
+  return rc;
+}
+
+// Device bytes gpf_predict_cov needs for Cp (padded) query columns: K_s and V (Np x Cp each), Sigma
+// (Cp x Cp), the vsq / vz partials (nt x Cp each), the coordinates and (mu | sd)
+static double pcov_bytes(const gpf_ctx* c, double Cp) {
+  return 8.0 * (2.0 * (double)c->Npad * Cp + Cp * Cp + (2.0 * c->nt + c->d + 2.0) * Cp);
+}
+
+int gpf_predict_cov(gpf_ctx* c, const double* ls, const double* xfit, int64_t M, double* mu, double* cov) {
+  if (!c) return GPF_BAD_ARG;
+  if (c->N <= 0) return bad_arg(c, "gpf_predict_cov: call gpf_set_data first");
+  if (M < 0) return bad_arg(c, "gpf_predict_cov: M < 0");
+  if (!ls) return bad_arg(c, "gpf_predict_cov: null length scales");
+  if (M > 0 && (!xfit || !mu || !cov)) return bad_arg(c, "gpf_predict_cov: null buffer");
+  for (int k = 0; k < c->d; ++k)
+    if (!(ls[k] > 0.0) || !std::isfinite(ls[k])) return bad_arg(c, "gpf_predict_cov: length scales must be finite and > 0");
+  if (M > (int64_t)1 << 24) return bad_arg(c, "gpf_predict_cov: M > 2^24 (Sigma is dense: M x M doubles)");
+  if (M == 0) return GPF_OK;
+  hipSetDevice(c->device);
+  if (c->K <= 0) c->K = 2;  // (as gpf_predict: the objective grid is not needed)
+  // the factorisation workspace first: a (re)allocation there frees the query buffers too
+  const Knobs knobs = Knobs::from_env();
+  if (int rw = ensure_work(c, 1, knobs)) return rw;
+  const int64_t Np = c->Npad;
+  const int nqt = (int)((M + T - 1) / T);
+  const int64_t Cp = (int64_t)nqt * T;
+  if (c->c_cols < Cp || c->c_np != Np || c->c_d != c->d || c->c_nt != c->nt) {
+    GPF_HIP(c, hipStreamSynchronize(c->stream));
+    free_pcov(c);
+    // no chunking over M: K_s, V and Sigma must fit half of free HBM together
+    size_t fr = 0, tot = 0;
+    GPF_HIP(c, hipMemGetInfo(&fr, &tot));
+    const double budget = 0.5 * (double)fr;
+    if (pcov_bytes(c, (double)Cp) > budget) {
+      int64_t fit = 0;  // the largest multiple of the tile that fits (pcov_bytes grows with Cp)
+      for (int64_t lo = 0, hi = Cp / T; lo < hi;) {
+        const int64_t mid = (lo + hi + 1) / 2;
+        if (pcov_bytes(c, (double)(mid * T)) <= budget) fit = mid * T, lo = mid; else hi = mid - 1;
+      }
+      c->err = "gpf_predict_cov: K_s, V and Sigma for M=" + std::to_string(M) + " at N=" + std::to_string(c->N) +
+               " need " + std::to_string((long long)(pcov_bytes(c, (double)Cp) / 1048576.0)) + " MiB, more than half of the free " +
+               std::to_string((long long)(fr / 1048576)) + " MiB of device memory; the largest M that fits is " + std::to_string(fit);
+      return GPF_BAD_ARG;
+    }
+    GPF_HIP(c, hipMalloc(&c->c_xf, (size_t)c->d * Cp * 8));
+    GPF_HIP(c, hipMalloc(&c->c_ks, (size_t)Np * Cp * 8));
+    GPF_HIP(c, hipMalloc(&c->c_v, (size_t)Np * Cp * 8));
+    GPF_HIP(c, hipMalloc(&c->c_cov, (size_t)Cp * Cp * 8));
+    GPF_HIP(c, hipMalloc(&c->c_vsq, (size_t)c->nt * Cp * 8));
+    GPF_HIP(c, hipMalloc(&c->c_vz, (size_t)c->nt * Cp * 8));
+    GPF_HIP(c, hipMalloc(&c->c_mu, (size_t)2 * Cp * 8));
+    GPF_HIP(c, hipHostMalloc((void**)&c->c_hx, (size_t)c->d * Cp * 8, hipHostMallocDefault));
+    GPF_HIP(c, hipHostMalloc((void**)&c->c_hmu, (size_t)Cp * 8, hipHostMallocDefault));
+    c->c_cols = Cp;
+    c->c_np = Np;
+    c->c_d = c->d;
+    c->c_nt = c->nt;
+  }
+  // the kept buffers may be wider than this call needs: every matrix of the call uses the leading
+  // dimension Cp of this call's padded M, so the results do not depend on what an earlier call left
+  std::memcpy(c->h_ls, ls, (size_t)c->d * 8);
+  GPF_HIP(c, hipMemcpyAsync(c->d_ls, c->h_ls, (size_t)c->d * 8, hipMemcpyHostToDevice, c->stream));
+  for (int k = 0; k < c->d; ++k) std::memcpy(c->c_hx + (size_t)k * Cp, xfit + (size_t)k * M, (size_t)M * 8);
+  GPF_HIP(c, hipMemcpyAsync(c->c_xf, c->c_hx, (size_t)c->d * Cp * 8, hipMemcpyHostToDevice, c->stream));
+  int rc = factor_single_async(c, nullptr, nullptr, knobs);
+  if (rc) return rc;
+  // K_s (Np x Cp, zero rows / columns past N / M) and K_ss into Sigma's buffer (zero past M)
+  rc = launch(c, PC_PREDK, 8.0 * Np * Cp + 8.0 * Cp * Cp, [&] {
+    gpf::launch_cross_cov(c->stream, (int)c->N, (int)M, (int)Np, (int)Cp, c->d, c->d_x, (int)c->N, c->c_xf, (int)Cp, c->d_ls,
+                          c->c_ks, Cp);
+    gpf::launch_cross_cov(c->stream, (int)M, (int)M, (int)Cp, (int)Cp, c->d, c->c_xf, (int)Cp, c->c_xf, (int)Cp, c->d_ls,
+                          c->c_cov, Cp);
+  });
+  // V = U K_s, stored (flops as gpf_predict counts them), and its per-column partials
+  const double vflops = 2.0 * T * T * (double)Cp * ((double)c->nt * (c->nt + 1) / 2) - (double)T * T * Cp * c->nt;
+  if (!rc)
+    rc = launch(c, PC_PRED, vflops, [&] {
+      hipLaunchKernelGGL(gpf::k_predict_v, dim3(nqt, c->nt), dim3(gpf::Geo<T>::NTH), 0, c->stream, (int)Np, c->d_U, c->c_ks,
+                         (int)Cp, c->c_vsq, c->d_yb, c->c_vz, c->c_v);
+    });
+  if (!rc)
+    rc = launch(c, PC_LOSS, 0.0, [&] {
+      hipLaunchKernelGGL(gpf::k_predict_out, dim3((unsigned)((M + NTHR - 1) / NTHR)), dim3(NTHR), 0, c->stream, c->nt, (int)M,
+                         c->c_vz, (int)Cp, c->c_vsq, c->c_mu, c->c_mu + Cp);
+    });
+  // Sigma's lower tiles, 2 T^2 Np flops each (the diagonal tiles counted in full, as k_lml_grad's):
+  // Np Cp^2 for the lower half plus Np Cp T for the diagonal tiles
+  const int ntile = nqt * (nqt + 1) / 2;
+  if (!rc)
+    rc = launch(c, PC_PRED, 2.0 * T * T * (double)Np * ntile, [&] {
+      hipLaunchKernelGGL(gpf::k_post_cov, dim3((unsigned)ntile), dim3(gpf::Geo<T>::NTH), 0, c->stream, (int)Np, nqt, c->c_v,
+                         (int)Cp, c->c_cov, Cp);
+    });
+  const int nmb = (int)((M + gpf::MIR_B - 1) / gpf::MIR_B);
+  if (!rc)
+    rc = launch(c, PC_PREDK, 8.0 * (double)M * M, [&] {
+      hipLaunchKernelGGL(gpf::k_mirror_lower, dim3((unsigned)(nmb * (nmb + 1) / 2)), dim3(NTHR), 0, c->stream, (int)M, c->c_cov,
+                         Cp);
+    });
+  if (!rc && hipMemcpyAsync(c->c_hmu, c->c_mu, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
+    rc = GPF_HIP_ERROR;
+    c->err = "gpf_predict_cov: copy back failed";
+  }
+  if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) {
+    rc = GPF_HIP_ERROR;
+    c->err = "gpf_predict_cov: synchronisation failed";
+  }
+  // the factorisation's status before anything reaches the caller's buffers
+  if (!rc) rc = particle_status(c, 0);
+  if (!rc) {
+    std::memcpy(mu, c->c_hmu, (size_t)M * 8);
+    if (hipMemcpy2DAsync(cov, (size_t)M * 8, c->c_cov, (size_t)Cp * 8, (size_t)M * 8, (size_t)M, hipMemcpyDeviceToHost,
+                         c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess) {
+      rc = GPF_HIP_ERROR;
+      c->err = "gpf_predict_cov: copy back failed";
+    }
+  }
+  if (c->prof) harvest(c);
+  if (pcov_bytes(c, (double)c->c_cols) > keep_bytes(knobs)) free_pcov(c);
   return rc;
 }
 

@@ -36,6 +36,7 @@ SIGNATURES = {
     "gpf_set_grid": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int, _dp, _dp]),
     "gpf_eval_batch": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _dp, _dp, _dp, _ip]),
     "gpf_predict": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int64, ctypes.c_int64, _dp, _dp]),
+    "gpf_predict_cov": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int64, _dp, _dp]),
     "gpf_kernel": (ctypes.c_int, [_vp, _dp, ctypes.c_int64, _dp, ctypes.c_int64, ctypes.c_int, _dp, _dp]),
     "gpf_log_marginal_likelihood": (ctypes.c_int, [_vp, _dp, _dp]),
     "gpf_lml_batch": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _dp, _dp, _ip, _ip]),
@@ -244,6 +245,23 @@ class Context:
         self._check(self.lib.gpf_predict(self._h, _ptr(ls), _ptr(xf), m, int(batch_size), _ptr(mu), _ptr(sd)),
                     "gpf_predict")
         return mu, sd
+
+    def predict_cov(self, lengths, x_fit):
+        """Joint latent posterior of the query points x_fit (d, M) (gpf_predict_cov):
+        (mu (M,), cov (M, M)), cov = K_ss - K_s^T Kn^-1 K_s exactly symmetric with an unclipped
+        diagonal; mu is bitwise predict()'s. LinAlgError if the covariance of the training points
+        is not positive definite, ValueError for bad arguments or an M whose dense cov does not
+        fit the device (the message names the largest M that does)."""
+        ls = _f64(lengths).reshape(-1)
+        xf = _f64(x_fit)
+        if xf.ndim != 2:
+            raise ValueError("x_fit must be (d, M)")
+        if self.d and (xf.shape[0] != self.d or ls.shape[0] != self.d):
+            raise ValueError(f"x_fit must be ({self.d}, M) and lengths ({self.d},)")
+        m = xf.shape[1]
+        mu, cov = np.empty(m), np.empty((m, m))
+        self._check(self.lib.gpf_predict_cov(self._h, _ptr(ls), _ptr(xf), m, _ptr(mu), _ptr(cov)), "gpf_predict_cov")
+        return mu, cov
 
     def kernel(self, x1, x2, l):
         a, b = _f64(x1), _f64(x2)

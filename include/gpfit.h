@@ -84,6 +84,26 @@ int gpf_eval_batch(gpf_ctx* ctx, const double* ls_Pd, int P, double* loss_P,
 int gpf_predict(gpf_ctx* ctx, const double* ls, const double* xfit_dM,
                 int64_t M, int64_t batch, double* mu_M, double* sd_M);
 
+/* Joint (latent, noise-free) posterior of the M query points xfit_dM (d, M):
+ *   mu_M[q] = K_s[:, q]^T alpha — bitwise gpf_predict's mean for the same inputs;
+ *   cov_MM  = K_ss - V^T V, V = L^-1 K_s: the full M x M row-major matrix, both triangles
+ *             written, exactly symmetric (the upper triangle is a copy of the lower).
+ * K_ss is kernel_func(xfit, xfit, l) with the diagonal exactly 1.0 (the prior variance,
+ * GP_func.py:34). The diagonal of cov_MM is NOT clipped at 1e-12 as gpf_predict's variance is
+ * (GP_func.py:39): where a query point coincides with another one or with a noise-free training
+ * point it can come out a few 1e-14 below zero; a caller that factorises cov_MM adds a jitter
+ * (gpfit.posterior.draws_from). No chunking over M: K_s and V (Npad x Mpad each) and Sigma
+ * (Mpad x Mpad) live on the device for the call; if they do not fit half of the free device
+ * memory the call returns GPF_BAD_ARG and gpf_last_error names the largest M that fits. The
+ * buffers are kept for the next call under GPF_PREDICT_KEEP_MB like gpf_predict's, and are
+ * apart from them: interleaved gpf_predict calls are not disturbed.
+ * GPF_NOT_PD as gpf_predict: mu_M and cov_MM are then untouched. GPF_BAD_ARG, before any
+ * device work: null ctx, no data set, M < 0, null ls, a null buffer with M > 0, a length scale
+ * that is not finite and > 0. M == 0 returns GPF_OK and writes nothing. Repeating a call on
+ * the same context and data gives the same bits (fixed-order sums, no floating-point atomics). */
+int gpf_predict_cov(gpf_ctx* ctx, const double* ls, const double* xfit_dM, int64_t M,
+                    double* mu_M, double* cov_MM);
+
 /* kernel_func(x1, x2, l) (GP_func.py:49-65): out is (N1, N2) row-major. */
 int gpf_kernel(gpf_ctx* ctx, const double* x1_dN1, int64_t N1,
                const double* x2_dN2, int64_t N2, int d, const double* l,
@@ -211,7 +231,9 @@ int gpf_set_profiling(gpf_ctx* ctx, int on);
  *  [12] factorisation wall ms (K build + diag + steps of all particle groups, which run
  *       on concurrent streams, so [0]/[3]/[6] may overlap)  [13] calls  [14] its flops
  *  [15] prediction V = U K_s kernel ms  [16] launches  [17] algorithmic flops
+ *       (gpf_predict_cov: its V = U K_s and Sigma = K_ss - V^T V kernels, one launch each)
  *  [18] prediction cross-covariance ms  [19] launches  [20] algorithmic bytes
+ *       (gpf_predict_cov: K_s and K_ss in one entry, and the mirror copy of Sigma's lower triangle)
  *  [21] probability-surface kernel ms  [22] launches  [23] algorithmic bytes
  *  [24] shader clock (MHz) the factor kernels held while they ran (every workgroup's span in
  *       s_memtime clocks over its span in the 100 MHz s_memrealtime clock; profiled batches only)
