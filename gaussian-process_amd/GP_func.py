@@ -52,11 +52,13 @@ def GP_cov(x_known, y_known, e_known, x_fit, lengths):
     return ctx.predict_cov(lengths, x_fit)
 
 
-def GP_draws(x_known, y_known, e_known, x_fit, lengths, n_draws, seed=None):
+def GP_draws(x_known, y_known, e_known, x_fit, lengths, n_draws, seed=None, method="host"):
     """n_draws joint draws of the latent GP at x_fit: (n_draws, M), from N(GP_cov's mu, cov) by a
-    host Cholesky factor of cov + jitter I (gpfit.posterior.draws_from; default_rng(seed))."""
+    Cholesky factor of cov + jitter I: method="host" takes it with NumPy from the copied-back cov
+    (gpfit.posterior.draws_from), method="device" on the GPU without cov leaving it
+    (gpf_posterior_draws). The normals are default_rng(seed)'s on both paths."""
     from gpfit.posterior import sample_posterior
-    return sample_posterior(x_known, y_known, e_known, x_fit, lengths, n_draws, seed=seed)[0]
+    return sample_posterior(x_known, y_known, e_known, x_fit, lengths, n_draws, seed=seed, method=method)[0]
 
 
 def kernel_func(x1, x2, l):

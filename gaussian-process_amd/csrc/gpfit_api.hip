@@ -26,6 +26,7 @@
 #include "gpf_objective.hip"
 #include "gpf_predict.hip"
 #include "gpf_postcov.hip"
+#include "gpf_densechol.hip"
 #include "gpf_lmlgrad.hip"
 #include "gpf_probsurf.hip"
 #include "gpf_hull.hip"
@@ -129,6 +130,17 @@ struct gpf_ctx {
   double *c_mu = nullptr, *c_hx = nullptr, *c_hmu = nullptr;
   int64_t c_cols = 0, c_np = 0;
   int c_d = 0, c_nt = 0;
+  // gpf_posterior_draws' buffers, apart from both of the above and kept under the same rule: a set like
+  // gpf_predict_cov's (g_cols columns), the factor L (g_cols x g_cols), the normals and the draws
+  // (g_rows x g_cols each) and the U_JJ strip (128 x g_cols + gpf::DC_JUNK) of the dense factorisation
+  double *g_xf = nullptr, *g_ks = nullptr, *g_v = nullptr, *g_cov = nullptr, *g_vsq = nullptr, *g_vz = nullptr;
+  double *g_mu = nullptr, *g_hx = nullptr, *g_hmu = nullptr;
+  double *g_L = nullptr, *g_z = nullptr, *g_dr = nullptr, *g_u = nullptr;
+  int64_t g_cols = 0, g_rows = 0, g_np = 0;
+  int g_d = 0, g_nt = 0;
+  // gpf_chol_dense's matrix, factor and U_JJ strip (grow-only, kept under the same rule); the status
+  // word of a dense factorisation sits behind its strip (dense_chol_strip_bytes)
+  Scratch dc_a, dc_l, dc_u;
   // gpf_prob_surface's row-chunk buffers, kept between calls like the prediction's
   double *s_t = nullptr, *s_cmp = nullptr, *s_y = nullptr, *s_p = nullptr;
   double4* s_info = nullptr;
@@ -257,8 +269,25 @@ static void free_pcov(gpf_ctx* c) {
   c->c_d = c->c_nt = 0;
 }
 
+static void free_pdraw(gpf_ctx* c) {
+  hipFree(c->g_xf); hipFree(c->g_ks); hipFree(c->g_v); hipFree(c->g_cov); hipFree(c->g_vsq); hipFree(c->g_vz);
+  hipFree(c->g_mu); hipFree(c->g_L); hipFree(c->g_z); hipFree(c->g_dr); hipFree(c->g_u);
+  hipHostFree(c->g_hx); hipHostFree(c->g_hmu);
+  c->g_xf = c->g_ks = c->g_v = c->g_cov = c->g_vsq = c->g_vz = c->g_mu = nullptr;
+  c->g_L = c->g_z = c->g_dr = c->g_u = nullptr;
+  c->g_hx = c->g_hmu = nullptr;
+  c->g_cols = c->g_rows = c->g_np = 0;
+  c->g_d = c->g_nt = 0;
+}
+
+static void free_dchol(gpf_ctx* c) {
+  for (Scratch* s : {&c->dc_a, &c->dc_l, &c->dc_u}) s->release();
+}
+
 static void free_pred(gpf_ctx* c) {
   free_pcov(c);
+  free_pdraw(c);
+  free_dchol(c);
   hipFree(c->p_xf); hipFree(c->p_ks); hipFree(c->p_vsq); hipFree(c->p_mu); hipFree(c->p_sd); hipFree(c->p_vz);
   hipHostFree(c->p_hx); hipHostFree(c->p_hout);
   c->p_xf = c->p_ks = c->p_vsq = c->p_mu = c->p_sd = c->p_vz = nullptr;
@@ -961,6 +990,65 @@ int gpf_predict(gpf_ctx* c, const double* ls, const double* xfit, int64_t M, int
   return rc;
 }
 
+// One set of gpf_predict_cov's device buffers (the context keeps two: gpf_predict_cov's own and
+// gpf_posterior_draws')
+struct PcovBufs {
+  double *xf, *ks, *v, *cov, *vsq, *vz, *mu, *hx;
+};
+
+// gpf_predict_cov's device pipeline, queued on the context's stream: the single-particle
+// factorisation, K_s and K_ss, V = U K_s with the mean's partials, the mean, Sigma's lower tiles and
+// the mirror copy. Leaves mu in b.mu and Sigma in b.cov (leading dimension Cp: symmetric, padded
+// diagonal 1, padding 0). gpf_posterior_draws runs the same launches in the same order, so its mean
+// is bitwise gpf_predict_cov's.
+static int pcov_enqueue(gpf_ctx* c, const Knobs& knobs, const double* ls, const double* xfit, int64_t M, int64_t Cp,
+                        const PcovBufs& b) {
+  const int64_t Np = c->Npad;
+  const int nqt = (int)(Cp / T);
+  // the kept buffers may be wider than this call needs: every matrix of the call uses the leading
+  // dimension Cp of this call's padded M, so the results do not depend on what an earlier call left
+  std::memcpy(c->h_ls, ls, (size_t)c->d * 8);
+  GPF_HIP(c, hipMemcpyAsync(c->d_ls, c->h_ls, (size_t)c->d * 8, hipMemcpyHostToDevice, c->stream));
+  for (int k = 0; k < c->d; ++k) std::memcpy(b.hx + (size_t)k * Cp, xfit + (size_t)k * M, (size_t)M * 8);
+  GPF_HIP(c, hipMemcpyAsync(b.xf, b.hx, (size_t)c->d * Cp * 8, hipMemcpyHostToDevice, c->stream));
+  int rc = factor_single_async(c, nullptr, nullptr, knobs);
+  if (rc) return rc;
+  // K_s (Np x Cp, zero rows / columns past N / M) and K_ss into Sigma's buffer (zero past M)
+  rc = launch(c, PC_PREDK, 8.0 * Np * Cp + 8.0 * Cp * Cp, [&] {
+    gpf::launch_cross_cov(c->stream, (int)c->N, (int)M, (int)Np, (int)Cp, c->d, c->d_x, (int)c->N, b.xf, (int)Cp, c->d_ls,
+                          b.ks, Cp);
+    gpf::launch_cross_cov(c->stream, (int)M, (int)M, (int)Cp, (int)Cp, c->d, b.xf, (int)Cp, b.xf, (int)Cp, c->d_ls,
+                          b.cov, Cp);
+  });
+  // V = U K_s, stored (flops as gpf_predict counts them), and its per-column partials
+  const double vflops = 2.0 * T * T * (double)Cp * ((double)c->nt * (c->nt + 1) / 2) - (double)T * T * Cp * c->nt;
+  if (!rc)
+    rc = launch(c, PC_PRED, vflops, [&] {
+      hipLaunchKernelGGL(gpf::k_predict_v, dim3(nqt, c->nt), dim3(gpf::Geo<T>::NTH), 0, c->stream, (int)Np, c->d_U, b.ks,
+                         (int)Cp, b.vsq, c->d_yb, b.vz, b.v);
+    });
+  if (!rc)
+    rc = launch(c, PC_LOSS, 0.0, [&] {
+      hipLaunchKernelGGL(gpf::k_predict_out, dim3((unsigned)((M + NTHR - 1) / NTHR)), dim3(NTHR), 0, c->stream, c->nt, (int)M,
+                         b.vz, (int)Cp, b.vsq, b.mu, b.mu + Cp);
+    });
+  // Sigma's lower tiles, 2 T^2 Np flops each (the diagonal tiles counted in full, as k_lml_grad's):
+  // Np Cp^2 for the lower half plus Np Cp T for the diagonal tiles
+  const int ntile = nqt * (nqt + 1) / 2;
+  if (!rc)
+    rc = launch(c, PC_PRED, 2.0 * T * T * (double)Np * ntile, [&] {
+      hipLaunchKernelGGL(gpf::k_post_cov, dim3((unsigned)ntile), dim3(gpf::Geo<T>::NTH), 0, c->stream, (int)Np, nqt, b.v,
+                         (int)Cp, b.cov, Cp);
+    });
+  const int nmb = (int)((M + gpf::MIR_B - 1) / gpf::MIR_B);
+  if (!rc)
+    rc = launch(c, PC_PREDK, 8.0 * (double)M * M, [&] {
+      hipLaunchKernelGGL(gpf::k_mirror_lower, dim3((unsigned)(nmb * (nmb + 1) / 2)), dim3(NTHR), 0, c->stream, (int)M, b.cov,
+                         Cp);
+    });
+  return rc;
+}
+
 // Device bytes gpf_predict_cov needs for Cp (padded) query columns: K_s and V (Np x Cp each), Sigma
 // (Cp x Cp), the vsq / vz partials (nt x Cp each), the coordinates and (mu | sd)
 static double pcov_bytes(const gpf_ctx* c, double Cp) {
@@ -1017,47 +1105,8 @@ int gpf_predict_cov(gpf_ctx* c, const double* ls, const double* xfit, int64_t M,
     c->c_d = c->d;
     c->c_nt = c->nt;
   }
-  // the kept buffers may be wider than this call needs: every matrix of the call uses the leading
-  // dimension Cp of this call's padded M, so the results do not depend on what an earlier call left
-  std::memcpy(c->h_ls, ls, (size_t)c->d * 8);
-  GPF_HIP(c, hipMemcpyAsync(c->d_ls, c->h_ls, (size_t)c->d * 8, hipMemcpyHostToDevice, c->stream));
-  for (int k = 0; k < c->d; ++k) std::memcpy(c->c_hx + (size_t)k * Cp, xfit + (size_t)k * M, (size_t)M * 8);
-  GPF_HIP(c, hipMemcpyAsync(c->c_xf, c->c_hx, (size_t)c->d * Cp * 8, hipMemcpyHostToDevice, c->stream));
-  int rc = factor_single_async(c, nullptr, nullptr, knobs);
-  if (rc) return rc;
-  // K_s (Np x Cp, zero rows / columns past N / M) and K_ss into Sigma's buffer (zero past M)
-  rc = launch(c, PC_PREDK, 8.0 * Np * Cp + 8.0 * Cp * Cp, [&] {
-    gpf::launch_cross_cov(c->stream, (int)c->N, (int)M, (int)Np, (int)Cp, c->d, c->d_x, (int)c->N, c->c_xf, (int)Cp, c->d_ls,
-                          c->c_ks, Cp);
-    gpf::launch_cross_cov(c->stream, (int)M, (int)M, (int)Cp, (int)Cp, c->d, c->c_xf, (int)Cp, c->c_xf, (int)Cp, c->d_ls,
-                          c->c_cov, Cp);
-  });
-  // V = U K_s, stored (flops as gpf_predict counts them), and its per-column partials
-  const double vflops = 2.0 * T * T * (double)Cp * ((double)c->nt * (c->nt + 1) / 2) - (double)T * T * Cp * c->nt;
-  if (!rc)
-    rc = launch(c, PC_PRED, vflops, [&] {
-      hipLaunchKernelGGL(gpf::k_predict_v, dim3(nqt, c->nt), dim3(gpf::Geo<T>::NTH), 0, c->stream, (int)Np, c->d_U, c->c_ks,
-                         (int)Cp, c->c_vsq, c->d_yb, c->c_vz, c->c_v);
-    });
-  if (!rc)
-    rc = launch(c, PC_LOSS, 0.0, [&] {
-      hipLaunchKernelGGL(gpf::k_predict_out, dim3((unsigned)((M + NTHR - 1) / NTHR)), dim3(NTHR), 0, c->stream, c->nt, (int)M,
-                         c->c_vz, (int)Cp, c->c_vsq, c->c_mu, c->c_mu + Cp);
-    });
-  // Sigma's lower tiles, 2 T^2 Np flops each (the diagonal tiles counted in full, as k_lml_grad's):
-  // Np Cp^2 for the lower half plus Np Cp T for the diagonal tiles
-  const int ntile = nqt * (nqt + 1) / 2;
-  if (!rc)
-    rc = launch(c, PC_PRED, 2.0 * T * T * (double)Np * ntile, [&] {
-      hipLaunchKernelGGL(gpf::k_post_cov, dim3((unsigned)ntile), dim3(gpf::Geo<T>::NTH), 0, c->stream, (int)Np, nqt, c->c_v,
-                         (int)Cp, c->c_cov, Cp);
-    });
-  const int nmb = (int)((M + gpf::MIR_B - 1) / gpf::MIR_B);
-  if (!rc)
-    rc = launch(c, PC_PREDK, 8.0 * (double)M * M, [&] {
-      hipLaunchKernelGGL(gpf::k_mirror_lower, dim3((unsigned)(nmb * (nmb + 1) / 2)), dim3(NTHR), 0, c->stream, (int)M, c->c_cov,
-                         Cp);
-    });
+  const PcovBufs bufs{c->c_xf, c->c_ks, c->c_v, c->c_cov, c->c_vsq, c->c_vz, c->c_mu, c->c_hx};
+  int rc = pcov_enqueue(c, knobs, ls, xfit, M, Cp, bufs);
   if (!rc && hipMemcpyAsync(c->c_hmu, c->c_mu, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
     rc = GPF_HIP_ERROR;
     c->err = "gpf_predict_cov: copy back failed";
@@ -1079,6 +1128,254 @@ int gpf_predict_cov(gpf_ctx* c, const double* ls, const double* xfit, int64_t M,
   }
   if (c->prof) harvest(c);
   if (pcov_bytes(c, (double)c->c_cols) > keep_bytes(knobs)) free_pcov(c);
+  return rc;
+}
+
+// ---- dense Cholesky on the device and posterior draws (gpf_densechol.hip) ----
+// The U_JJ strip of a dense factorisation with leading dimension ld: 128 x ld doubles, factor128's
+// throw-away outputs (gpf::DC_JUNK doubles) and the status word (one int in a double's slot)
+static size_t dense_chol_strip_bytes(int64_t ld) { return ((size_t)T * (size_t)ld + gpf::DC_JUNK + 1) * 8; }
+
+// The jitter ladder over a device matrix, the one place it lives (gpf_chol_dense and
+// gpf_posterior_draws both end here): A (npad x ld, lower triangle read, identity padding; not
+// modified) -> L (npad x ld, lower tiles) with L L^T = A + jitters[t] I for the first t that
+// factorises: the working copy, then three launches per block column on the context's stream
+// (gpf_densechol.hip). strip: dense_chol_strip_bytes(ld), zeroed here. Every attempt runs to its end
+// and is judged by one status word read back afterwards.
+// Returns GPF_OK with *jitter_used / *tries set, or GPF_NOT_PD with *tries = nj.
+static int dense_chol_ladder(gpf_ctx* c, const double* dA, double* dL, double* strip, int64_t n, int64_t ld,
+                             const double* jitters, int nj, double* jitter_used, int* tries) {
+  const int nt = (int)((n + T - 1) / T);
+  double* junk = strip + (size_t)T * ld;
+  int* dinfo = reinterpret_cast<int*>(junk + gpf::DC_JUNK);
+  GPF_HIP(c, hipMemsetAsync(junk, 0, (gpf::DC_JUNK + 1) * 8, c->stream));
+  for (int t = 0; t < nj; ++t) {
+    if (t > 0) GPF_HIP(c, hipMemsetAsync(dinfo, 0, 4, c->stream));
+    const double jit = jitters[t];
+    const int ntile = nt * (nt + 1) / 2;
+    int rc = launch(c, PC_PREDK, 16.0 * T * T * ntile, [&] {
+      hipLaunchKernelGGL(gpf::k_dc_init, dim3(ntile), dim3(gpf::DNTH), 0, c->stream, nt, (int)n, jit, dA, dL, (int)ld);
+    });
+    for (int J = 0; J < nt && !rc; ++J) {
+      const int m = nt - 1 - J;
+      rc = launch(c, PC_PRED, 2.0 / 3.0 * T * T * (double)T, [&] {  // potrf + trtri of the block
+        hipLaunchKernelGGL(gpf::k_dc_diag, dim3(1), dim3(gpf::DNTH), 0, c->stream, J, dL, strip, (int)ld, junk, dinfo);
+      });
+      if (!rc && m > 0)
+        rc = launch(c, PC_PRED, (double)T * T * T * m, [&] {
+          hipLaunchKernelGGL(gpf::k_dc_finish, dim3(m), dim3(gpf::DNTH), 0, c->stream, J, dL, strip, (int)ld);
+        });
+      if (!rc && m > 0)  // 2 T^3 per tile below the diagonal, T^3 per diagonal tile
+        rc = launch(c, PC_PRED, (double)T * T * T * m * m, [&] {
+          hipLaunchKernelGGL(gpf::k_dc_trail, dim3(m * (m + 1) / 2), dim3(gpf::DNTH), 0, c->stream, J, m, dL, (int)ld);
+        });
+    }
+    if (rc) return rc;
+    int info = 0;
+    GPF_HIP(c, hipMemcpyAsync(&info, dinfo, 4, hipMemcpyDeviceToHost, c->stream));
+    GPF_HIP(c, hipStreamSynchronize(c->stream));
+    if (info == 0) {
+      *jitter_used = jit;
+      *tries = t + 1;
+      return GPF_OK;
+    }
+  }
+  *tries = nj;
+  c->err = "Matrix is not positive definite";
+  return GPF_NOT_PD;
+}
+
+static const char* ladder_arg_error(const double* jitters, int nj) {
+  if (!jitters || nj < 1) return "needs at least one jitter";
+  for (int t = 0; t < nj; ++t)
+    if (!std::isfinite(jitters[t])) return "jitters must be finite";
+  return nullptr;
+}
+
+int gpf_chol_dense(gpf_ctx* c, const double* A, int64_t n, const double* jitters, int nj, double* L, double* jitter_used,
+                   int* tries) {
+  if (!c) return GPF_BAD_ARG;
+  if (n < 0) return bad_arg(c, "gpf_chol_dense: n < 0");
+  if (!jitter_used || !tries) return bad_arg(c, "gpf_chol_dense: null buffer");
+  if (const char* m = ladder_arg_error(jitters, nj)) {
+    c->err = std::string("gpf_chol_dense: ") + m;
+    return GPF_BAD_ARG;
+  }
+  if (n > 0 && (!A || !L)) return bad_arg(c, "gpf_chol_dense: null buffer");
+  if (n > (int64_t)1 << 24) return bad_arg(c, "gpf_chol_dense: n > 2^24");
+  if (n == 0) return GPF_OK;
+  hipSetDevice(c->device);
+  const Knobs knobs = Knobs::from_env();
+  const int64_t np = ((n + T - 1) / T) * T;  // rows and leading dimension of this call's matrices
+  const double need = 2.0 * 8.0 * (double)np * np + (double)dense_chol_strip_bytes(np);
+  if ((size_t)np * np * 8 > c->dc_a.cap) {
+    GPF_HIP(c, hipStreamSynchronize(c->stream));
+    free_dchol(c);
+    size_t fr = 0, tot = 0;
+    GPF_HIP(c, hipMemGetInfo(&fr, &tot));
+    if (need > 0.5 * (double)fr) {
+      const int64_t fit = (int64_t)(std::sqrt(0.5 * (double)fr / 16.0) / T) * T - T;
+      c->err = "gpf_chol_dense: the matrix and its factor for n=" + std::to_string(n) + " need " +
+               std::to_string((long long)(need / 1048576.0)) + " MiB, more than half of the free " +
+               std::to_string((long long)(fr / 1048576)) + " MiB of device memory; the largest n that fits is " +
+               std::to_string(std::max<int64_t>(fit, 0));
+      return GPF_BAD_ARG;
+    }
+  }
+  int rc = c->dc_a.grow(c, (size_t)np * np * 8, false, true);
+  if (!rc) rc = c->dc_l.grow(c, (size_t)np * np * 8, false, true);
+  if (!rc) rc = c->dc_u.grow(c, dense_chol_strip_bytes(np), false, true);
+  if (rc) return rc;
+  double *dA = c->dc_a.as<double>(), *dL = c->dc_l.as<double>();
+  // A zero-padded with an identity block; L's tiles above the diagonal are never written by the
+  // factorisation: zero for the copy back
+  GPF_HIP(c, hipMemsetAsync(dA, 0, (size_t)np * np * 8, c->stream));
+  GPF_HIP(c, hipMemsetAsync(dL, 0, (size_t)np * np * 8, c->stream));
+  GPF_HIP(c, hipMemcpy2DAsync(dA, (size_t)np * 8, A, (size_t)n * 8, (size_t)n * 8, (size_t)n, hipMemcpyHostToDevice, c->stream));
+  rc = launch(c, PC_PREDK, 8.0 * (double)n * n, [&] {
+    hipLaunchKernelGGL(gpf::k_dc_pad_diag, dim3(1), dim3(T), 0, c->stream, (int)n, (int)np, dA, np);
+  });
+  double jit = 0.0;
+  int tr = 0;
+  if (!rc) rc = dense_chol_ladder(c, dA, dL, c->dc_u.as<double>(), n, np, jitters, nj, &jit, &tr);
+  if (rc == GPF_OK) {
+    if (hipMemcpy2DAsync(L, (size_t)n * 8, dL, (size_t)np * 8, (size_t)n * 8, (size_t)n, hipMemcpyDeviceToHost, c->stream) !=
+            hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess) {
+      rc = GPF_HIP_ERROR;
+      c->err = "gpf_chol_dense: copy back failed";
+    }
+  }
+  if (rc == GPF_OK) *jitter_used = jit;
+  if (rc == GPF_OK || rc == GPF_NOT_PD) *tries = tr;
+  hipStreamSynchronize(c->stream);
+  if (c->prof) harvest(c);
+  if (need > keep_bytes(knobs)) free_dchol(c);
+  return rc;
+}
+
+// Device bytes gpf_posterior_draws needs: gpf_predict_cov's for Cp columns, the factor L (Cp x Cp),
+// the normals and the draws (Sp x Cp each) and the U_JJ strip
+static double pdraw_bytes(const gpf_ctx* c, double Cp, double Sp) {
+  return pcov_bytes(c, Cp) + 8.0 * (Cp * Cp + 2.0 * Sp * Cp + (double)T * Cp + gpf::DC_JUNK + 1);
+}
+
+int gpf_posterior_draws(gpf_ctx* c, const double* ls, const double* xfit, int64_t M, const double* z, int64_t S,
+                        const double* jitters, int nj, double* mu, double* draws, double* chol, double* jitter_used,
+                        int* tries) {
+  if (!c) return GPF_BAD_ARG;
+  if (c->N <= 0) return bad_arg(c, "gpf_posterior_draws: call gpf_set_data first");
+  if (M < 0 || S < 0) return bad_arg(c, "gpf_posterior_draws: M < 0 or S < 0");
+  if (!ls) return bad_arg(c, "gpf_posterior_draws: null length scales");
+  if (!jitter_used || !tries) return bad_arg(c, "gpf_posterior_draws: null buffer");
+  if (const char* m = ladder_arg_error(jitters, nj)) {
+    c->err = std::string("gpf_posterior_draws: ") + m;
+    return GPF_BAD_ARG;
+  }
+  if (M > 0 && (!xfit || !mu)) return bad_arg(c, "gpf_posterior_draws: null buffer");
+  if (M > 0 && S > 0 && (!z || !draws)) return bad_arg(c, "gpf_posterior_draws: null buffer");
+  for (int k = 0; k < c->d; ++k)
+    if (!(ls[k] > 0.0) || !std::isfinite(ls[k])) return bad_arg(c, "gpf_posterior_draws: length scales must be finite and > 0");
+  if (M > (int64_t)1 << 24 || S > (int64_t)1 << 24) return bad_arg(c, "gpf_posterior_draws: M or S > 2^24");
+  if (M == 0 || S == 0) return GPF_OK;
+  hipSetDevice(c->device);
+  if (c->K <= 0) c->K = 2;  // (as gpf_predict: the objective grid is not needed)
+  // the factorisation workspace first: a (re)allocation there frees the query buffers too
+  const Knobs knobs = Knobs::from_env();
+  if (int rw = ensure_work(c, 1, knobs)) return rw;
+  const int64_t Np = c->Npad;
+  const int nqt = (int)((M + T - 1) / T), nst = (int)((S + T - 1) / T);
+  const int64_t Cp = (int64_t)nqt * T, Sp = (int64_t)nst * T;
+  if (c->g_cols < Cp || c->g_rows < Sp || c->g_np != Np || c->g_d != c->d || c->g_nt != c->nt) {
+    GPF_HIP(c, hipStreamSynchronize(c->stream));
+    free_pdraw(c);
+    // no chunking over M: everything must fit half of free HBM together
+    size_t fr = 0, tot = 0;
+    GPF_HIP(c, hipMemGetInfo(&fr, &tot));
+    const double budget = 0.5 * (double)fr;
+    if (pdraw_bytes(c, (double)Cp, (double)Sp) > budget) {
+      int64_t fit = 0;  // the largest multiple of the tile that fits with this S
+      for (int64_t lo = 0, hi = Cp / T; lo < hi;) {
+        const int64_t mid = (lo + hi + 1) / 2;
+        if (pdraw_bytes(c, (double)(mid * T), (double)Sp) <= budget) fit = mid * T, lo = mid; else hi = mid - 1;
+      }
+      c->err = "gpf_posterior_draws: K_s, V, Sigma, its factor and the draws for M=" + std::to_string(M) + ", S=" +
+               std::to_string(S) + " at N=" + std::to_string(c->N) + " need " +
+               std::to_string((long long)(pdraw_bytes(c, (double)Cp, (double)Sp) / 1048576.0)) + " MiB, more than half of the free " +
+               std::to_string((long long)(fr / 1048576)) + " MiB of device memory; the largest M that fits is " + std::to_string(fit);
+      return GPF_BAD_ARG;
+    }
+    GPF_HIP(c, hipMalloc(&c->g_xf, (size_t)c->d * Cp * 8));
+    GPF_HIP(c, hipMalloc(&c->g_ks, (size_t)Np * Cp * 8));
+    GPF_HIP(c, hipMalloc(&c->g_v, (size_t)Np * Cp * 8));
+    GPF_HIP(c, hipMalloc(&c->g_cov, (size_t)Cp * Cp * 8));
+    GPF_HIP(c, hipMalloc(&c->g_vsq, (size_t)c->nt * Cp * 8));
+    GPF_HIP(c, hipMalloc(&c->g_vz, (size_t)c->nt * Cp * 8));
+    GPF_HIP(c, hipMalloc(&c->g_mu, (size_t)2 * Cp * 8));
+    GPF_HIP(c, hipMalloc(&c->g_L, (size_t)Cp * Cp * 8));
+    GPF_HIP(c, hipMalloc(&c->g_z, (size_t)Sp * Cp * 8));
+    GPF_HIP(c, hipMalloc(&c->g_dr, (size_t)Sp * Cp * 8));
+    GPF_HIP(c, hipMalloc(&c->g_u, dense_chol_strip_bytes(Cp)));
+    GPF_HIP(c, hipHostMalloc((void**)&c->g_hx, (size_t)c->d * Cp * 8, hipHostMallocDefault));
+    GPF_HIP(c, hipHostMalloc((void**)&c->g_hmu, (size_t)Cp * 8, hipHostMallocDefault));
+    c->g_cols = Cp;
+    c->g_rows = Sp;
+    c->g_np = Np;
+    c->g_d = c->d;
+    c->g_nt = c->nt;
+  }
+  // (as in gpf_predict_cov, every matrix of the call uses this call's Cp as its leading dimension)
+  // the mean's padding is read by k_draws for the padded columns only: finite, not uninitialised
+  GPF_HIP(c, hipMemsetAsync(c->g_mu, 0, (size_t)Cp * 8, c->stream));
+  const PcovBufs bufs{c->g_xf, c->g_ks, c->g_v, c->g_cov, c->g_vsq, c->g_vz, c->g_mu, c->g_hx};
+  int rc = pcov_enqueue(c, knobs, ls, xfit, M, Cp, bufs);
+  if (!rc && hipMemcpyAsync(c->g_hmu, c->g_mu, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
+    rc = GPF_HIP_ERROR;
+    c->err = "gpf_posterior_draws: copy back failed";
+  }
+  // the normals, zero-padded to Sp x Cp (behind the pipeline's launches on the stream; pageable source)
+  if (!rc && (hipMemsetAsync(c->g_z, 0, (size_t)Sp * Cp * 8, c->stream) != hipSuccess ||
+              hipMemcpy2DAsync(c->g_z, (size_t)Cp * 8, z, (size_t)M * 8, (size_t)M * 8, (size_t)S, hipMemcpyHostToDevice,
+                               c->stream) != hipSuccess)) {
+    rc = GPF_HIP_ERROR;
+    c->err = "gpf_posterior_draws: upload of the normals failed";
+  }
+  if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) {
+    rc = GPF_HIP_ERROR;
+    c->err = "gpf_posterior_draws: synchronisation failed";
+  }
+  // the training factorisation's status before the dense one starts
+  if (!rc) rc = particle_status(c, 0);
+  double jit = 0.0;
+  int tr = 0;
+  if (!rc && chol) rc = hipMemsetAsync(c->g_L, 0, (size_t)Cp * Cp * 8, c->stream) == hipSuccess ? GPF_OK : GPF_HIP_ERROR;
+  const bool laddered = !rc;
+  if (!rc) rc = dense_chol_ladder(c, c->g_cov, c->g_L, c->g_u, M, Cp, jitters, nj, &jit, &tr);
+  if (!rc)  // 2 T^2 flops per 128-deep step of a tile, depth 128 (I + 1)
+    rc = launch(c, PC_PRED, 2.0 * T * T * (double)T * nst * ((double)nqt * (nqt + 1) / 2), [&] {
+      hipLaunchKernelGGL(gpf::k_draws, dim3(nst, nqt), dim3(gpf::DNTH), 0, c->stream, nqt, c->g_z, (int)Cp, c->g_L, (int)Cp,
+                         c->g_mu, c->g_dr);
+    });
+  if (!rc) {
+    // nothing of size M x M leaves the device unless the caller asks for the factor
+    bool ok = hipMemcpy2DAsync(draws, (size_t)M * 8, c->g_dr, (size_t)Cp * 8, (size_t)M * 8, (size_t)S, hipMemcpyDeviceToHost,
+                               c->stream) == hipSuccess;
+    if (ok && chol)
+      ok = hipMemcpy2DAsync(chol, (size_t)M * 8, c->g_L, (size_t)Cp * 8, (size_t)M * 8, (size_t)M, hipMemcpyDeviceToHost,
+                            c->stream) == hipSuccess;
+    if (!ok || hipStreamSynchronize(c->stream) != hipSuccess) {
+      rc = GPF_HIP_ERROR;
+      c->err = "gpf_posterior_draws: copy back failed";
+    }
+  }
+  if (!rc) {
+    std::memcpy(mu, c->g_hmu, (size_t)M * 8);
+    *jitter_used = jit;
+  }
+  if (laddered && (rc == GPF_OK || rc == GPF_NOT_PD)) *tries = tr;
+  hipStreamSynchronize(c->stream);
+  if (c->prof) harvest(c);
+  if (pdraw_bytes(c, (double)c->g_cols, (double)c->g_rows) > keep_bytes(knobs)) free_pdraw(c);
   return rc;
 }
 

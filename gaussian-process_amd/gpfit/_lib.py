@@ -37,6 +37,9 @@ SIGNATURES = {
     "gpf_eval_batch": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _dp, _dp, _dp, _ip]),
     "gpf_predict": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int64, ctypes.c_int64, _dp, _dp]),
     "gpf_predict_cov": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int64, _dp, _dp]),
+    "gpf_chol_dense": (ctypes.c_int, [_vp, _dp, ctypes.c_int64, _dp, ctypes.c_int, _dp, _dp, _ip]),
+    "gpf_posterior_draws": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int64, _dp, ctypes.c_int64, _dp, ctypes.c_int,
+                                           _dp, _dp, _dp, _dp, _ip]),
     "gpf_kernel": (ctypes.c_int, [_vp, _dp, ctypes.c_int64, _dp, ctypes.c_int64, ctypes.c_int, _dp, _dp]),
     "gpf_log_marginal_likelihood": (ctypes.c_int, [_vp, _dp, _dp]),
     "gpf_lml_batch": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _dp, _dp, _ip, _ip]),
@@ -123,6 +126,35 @@ def _f64(a):
 
 def _ptr(a):
     return a.ctypes.data_as(_dp)
+
+
+JITTERS = (1e-12, 1e-10, 1e-8, 1e-6)   # gpfit.posterior's ladder: GP_func.py:39's variance floor, x 100 per failure
+
+
+def check_jitters(jitters):
+    """The jitter ladder as a (nj,) float64 array; ValueError if it is empty, not one-dimensional,
+    not finite, negative or not strictly ascending (checked before the library is touched)."""
+    j = np.array(jitters, dtype=np.float64, ndmin=1)
+    if j.ndim != 1 or j.size < 1:
+        raise ValueError("jitters must be a non-empty sequence")
+    if not np.all(np.isfinite(j)) or np.any(j < 0.0):
+        raise ValueError("jitters must be finite and >= 0")
+    if np.any(np.diff(j) <= 0.0):
+        raise ValueError("jitters must be strictly ascending")
+    return np.ascontiguousarray(j)
+
+
+def check_draw_args(d, lengths, x_fit, z, jitters):
+    """Shapes and ladder of a posterior_draws call against the data's dimensionality d, before the
+    library is touched: (ls (d,), xf (d, M), z (S, M), jitters (nj,)) as contiguous float64 arrays;
+    ValueError otherwise."""
+    j = check_jitters(jitters)
+    ls, xf, z = _f64(lengths).reshape(-1), _f64(x_fit), _f64(z)
+    if xf.ndim != 2 or xf.shape[0] != d or ls.shape[0] != d:
+        raise ValueError(f"x_fit must be ({d}, M) and lengths ({d},)")
+    if z.ndim != 2 or z.shape[1] != xf.shape[1]:
+        raise ValueError(f"z must be (S, {xf.shape[1]})")
+    return ls, xf, z, j
 
 
 def _digest(*arrays):
@@ -262,6 +294,62 @@ class Context:
         mu, cov = np.empty(m), np.empty((m, m))
         self._check(self.lib.gpf_predict_cov(self._h, _ptr(ls), _ptr(xf), m, _ptr(mu), _ptr(cov)), "gpf_predict_cov")
         return mu, cov
+
+    def chol_dense(self, a, jitters=JITTERS):
+        """Cholesky factor of the dense symmetric matrix a (n, n) on the device (gpf_chol_dense):
+        (L (n, n) with zeros above the diagonal, info), L L^T = a + jitter I for the first jitter of
+        the ladder that factorises; info: "jitter" and "tries". Only a's lower triangle is read.
+        LinAlgError (with .tries) if every jitter fails, ValueError for a bad shape or ladder."""
+        j = check_jitters(jitters)
+        a = _f64(a)
+        if a.ndim != 2 or a.shape[0] != a.shape[1]:
+            raise ValueError("a must be a square matrix")
+        n = a.shape[0]
+        L = np.empty((n, n))
+        jit, tries = ctypes.c_double(0.0), ctypes.c_int(0)
+        rc = self.lib.gpf_chol_dense(self._h, _ptr(a), n, _ptr(j), int(j.size), _ptr(L), ctypes.byref(jit),
+                                     ctypes.byref(tries))
+        self._check_ladder(rc, "gpf_chol_dense", tries)
+        if n == 0:
+            return L, {"jitter": float(j[0]), "tries": 0}
+        return L, {"jitter": float(jit.value), "tries": int(tries.value)}
+
+    def _check_ladder(self, rc, what, tries):
+        try:
+            self._check(rc, what)
+        except np.linalg.LinAlgError as err:
+            err.tries = int(tries.value)
+            raise
+
+    def posterior_draws(self, lengths, x_fit, z, jitters=JITTERS, want_chol=False, out=None):
+        """Joint draws of the latent posterior at x_fit (d, M) from the normals z (S, M), Sigma and
+        its factor staying on the device (gpf_posterior_draws): (mu (M,), draws (S, M), info).
+        mu is bitwise predict_cov()'s; draws = mu + z L^T, L L^T = Sigma + jitter I. info: "jitter",
+        "tries" and, with want_chol, "chol" (M, M). ``out`` = (mu, draws) float64 arrays to write into.
+        LinAlgError if the training covariance is not positive definite or every jitter fails (the
+        outputs are then untouched), ValueError for bad shapes, a bad ladder or an M that does not
+        fit the device."""
+        if not self.d:
+            raise ValueError("posterior_draws: call set_data first")
+        ls, xf, z, j = check_draw_args(self.d, lengths, x_fit, z, jitters)
+        m, s = xf.shape[1], z.shape[0]
+        if out is None:
+            mu, draws = np.empty(m), np.empty((s, m))
+        else:
+            mu, draws = out
+            if (mu.shape != (m,) or draws.shape != (s, m) or mu.dtype != np.float64 or draws.dtype != np.float64
+                    or not mu.flags.c_contiguous or not draws.flags.c_contiguous):
+                raise ValueError(f"out must be C-contiguous float64 arrays ({m},) and ({s}, {m})")
+        chol = np.empty((m, m)) if want_chol else None
+        jit, tries = ctypes.c_double(0.0), ctypes.c_int(0)
+        rc = self.lib.gpf_posterior_draws(self._h, _ptr(ls), _ptr(xf), m, _ptr(z), s, _ptr(j), int(j.size), _ptr(mu),
+                                          _ptr(draws), _ptr(chol) if want_chol else None, ctypes.byref(jit),
+                                          ctypes.byref(tries))
+        self._check_ladder(rc, "gpf_posterior_draws", tries)
+        info = {"jitter": float(jit.value), "tries": int(tries.value)}
+        if want_chol:
+            info["chol"] = chol
+        return mu, draws, info
 
     def kernel(self, x1, x2, l):
         a, b = _f64(x1), _f64(x2)

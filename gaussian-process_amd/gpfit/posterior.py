@@ -7,14 +7,18 @@ Sigma = K_ss - K_s^T Kn^-1 K_s (``Context.predict_cov``, gpf_predict_cov), or dr
 N(mu, Sigma):
 
   ``draws_from(mu, cov, ...)``        draws = mu + z L^T, L = cholesky(cov + jitter I) on the host;
-  ``sample_posterior(x, y, e, ...)``  the device's (mu, cov) of the query points, then draws_from.
+  ``sample_posterior(x, y, e, ...)``  method="host": the device's (mu, cov) of the query points, then
+                                      draws_from; method="device": Sigma, its factor and the product
+                                      stay on the device (``Context.posterior_draws``).
 
 Sigma is latent (noise-free) and its diagonal is not clipped: where query points coincide with
 each other or with a noise-free training point it is singular up to rounding. The jitter starts
 at 1e-12, the reference's own variance floor (GP_func.py:39), and is multiplied by 100 after every
 failed factorisation up to 1e-6; a matrix that still fails is not a covariance and the
-LinAlgError is raised. The Cholesky factor of Sigma is taken on the host (NumPy): the device's
-factorisation kernels build their matrix from coordinates and cannot take a dense input.
+LinAlgError is raised. With method="host" the Cholesky factor of Sigma is taken by NumPy, which
+costs a copy of the whole M x M matrix and an O(M^3) host factorisation; method="device" runs the
+same ladder with the dense blocked factorisation of gpf_densechol.hip (gpf_posterior_draws) and
+copies only the mean and the draws back. Both paths draw the same normals from a seed.
 
 Model: fixed amplitude 1, fixed noise e^2, ARD squared-exponential, as GP_func.py.
 """
@@ -22,9 +26,9 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._lib import default_context
+from ._lib import JITTERS, check_jitters, default_context   # JITTERS: from GP_func.py:39's variance floor, x 100 per failure
 
-JITTERS = (1e-12, 1e-10, 1e-8, 1e-6)   # from GP_func.py:39's variance floor, x 100 per failure
+METHODS = ("host", "device")
 
 
 def draws_from(mu, cov, n_draws=1, seed=None, z=None):
@@ -56,15 +60,37 @@ def draws_from(mu, cov, n_draws=1, seed=None, z=None):
     return mu + z @ L.T, {"jitter": jitter, "tries": tries}
 
 
-def sample_posterior(x_known, y_known, e_known, x_fit, lengths, n_draws, seed=None, ctx=None, mean_and_cov=None):
+def sample_posterior(x_known, y_known, e_known, x_fit, lengths, n_draws, seed=None, ctx=None, mean_and_cov=None,
+                     method="host", jitters=JITTERS):
     """n_draws joint draws of the latent GP at x_fit (d, M): (draws (n_draws, M), info).
 
-    ``mean_and_cov(x_fit, lengths) -> (mu (M,), cov (M, M))`` injects an evaluator (the CPU tests);
-    the default is gpf_predict_cov on this process's GPU after set_data(x_known, y_known, e_known).
-    info: draws_from's, plus "mu" and "cov".
+    method="host" (the default): ``mean_and_cov(x_fit, lengths) -> (mu (M,), cov (M, M))`` injects
+    an evaluator (the CPU tests); the default is gpf_predict_cov on this process's GPU after
+    set_data(x_known, y_known, e_known). info: draws_from's, plus "mu" and "cov".
+
+    method="device": gpf_posterior_draws on this process's GPU; Sigma never reaches the host. The
+    normals are default_rng(seed).standard_normal((n_draws, M)), exactly draws_from's, so a seed
+    means the same normals on both paths. ``jitters`` is the ladder (ascending, >= 0). info: "mu",
+    "jitter", "tries"; no "cov".
     """
+    if method not in METHODS:
+        raise ValueError(f"method must be one of {METHODS}, not {method!r}")
     x_fit = np.asarray(x_fit, dtype=np.float64)
     lengths = np.asarray(lengths, dtype=np.float64).reshape(-1)
+    if method == "device":
+        if mean_and_cov is not None:
+            raise ValueError('mean_and_cov injects a host evaluator: use method="host"')
+        jitters = check_jitters(jitters)
+        x_known = np.asarray(x_known, dtype=np.float64)
+        if x_fit.ndim != 2 or x_known.ndim != 2 or x_fit.shape[0] != x_known.shape[0]:
+            raise ValueError("x_fit must be (d, M) with the same d as x_known")
+        z = np.random.default_rng(seed).standard_normal((int(n_draws), x_fit.shape[1]))
+        if ctx is None:
+            ctx = default_context()
+        ctx.set_data(x_known, y_known, e_known)
+        mu, draws, info = ctx.posterior_draws(lengths, x_fit, z, jitters=jitters)
+        info["mu"] = mu
+        return draws, info
     if mean_and_cov is None:
         x_known = np.asarray(x_known, dtype=np.float64)
         if x_fit.ndim != 2 or x_fit.shape[0] != x_known.shape[0]:

@@ -104,6 +104,37 @@ int gpf_predict(gpf_ctx* ctx, const double* ls, const double* xfit_dM,
 int gpf_predict_cov(gpf_ctx* ctx, const double* ls, const double* xfit_dM, int64_t M,
                     double* mu_M, double* cov_MM);
 
+/* Cholesky factor of a dense symmetric host matrix on the device: tries A + jitters[t] I for
+ * t = 0, 1, .. until one factorises. L_nn: n x n row-major, zeros above the diagonal.
+ * Only A's lower triangle is read. A blocked left-looking factorisation on 128-tiles with FP64
+ * MFMA (gpf_densechol.hip), three launches per block column, A kept intact on the device between
+ * the attempts. *jitter_used is the value that factorised, *tries the number of attempts.
+ * GPF_NOT_PD if every jitter failed: L_nn and *jitter_used are untouched and *tries = nj.
+ * GPF_BAD_ARG, before any device work: null ctx or buffer, n < 0, nj < 1, a non-finite jitter, or
+ * a matrix that does not fit half of the free device memory with its factor. n == 0 returns GPF_OK.
+ * Needs no gpf_set_data. The same bits on every call (fixed-order sums, no floating-point atomics). */
+int gpf_chol_dense(gpf_ctx* ctx, const double* A_nn, int64_t n, const double* jitters, int nj,
+                   double* L_nn, double* jitter_used, int* tries);
+
+/* S joint draws of the latent posterior at M query points without Sigma leaving the device:
+ * gpf_predict_cov's pipeline up to k_post_cov, the dense factorisation above with the same
+ * jitter ladder, draws = mu + z L^T. z_SM: (S, M) standard normals from the caller.
+ * chol_MM nullable: the factor that was used (M x M row-major), for callers and tests.
+ * mu_M is bitwise gpf_predict_cov's (the same kernels in the same order). Nothing of size M x M is
+ * copied to the host unless chol_MM is given. No chunking over M: gpf_predict_cov's buffers, the
+ * factor (Mpad x Mpad), the normals and the draws (Spad x Mpad each) and a 128 x Mpad scratch must
+ * fit half of the free device memory, else GPF_BAD_ARG and gpf_last_error names the largest M
+ * that fits. The buffers are kept under GPF_PREDICT_KEEP_MB, apart from gpf_predict's and
+ * gpf_predict_cov's. GPF_NOT_PD if the training covariance is not positive definite (as
+ * gpf_predict_cov) or every jitter failed (*tries = nj): the outputs are then untouched.
+ * GPF_BAD_ARG, before any device work: null ctx, no data set, M < 0 or S < 0, null ls, a null
+ * buffer, nj < 1, a non-finite jitter, a length scale that is not finite and > 0. M == 0 or
+ * S == 0 returns GPF_OK and writes nothing. */
+int gpf_posterior_draws(gpf_ctx* ctx, const double* ls, const double* xfit_dM, int64_t M,
+                        const double* z_SM, int64_t S, const double* jitters, int nj,
+                        double* mu_M, double* draws_SM, double* chol_MM,
+                        double* jitter_used, int* tries);
+
 /* kernel_func(x1, x2, l) (GP_func.py:49-65): out is (N1, N2) row-major. */
 int gpf_kernel(gpf_ctx* ctx, const double* x1_dN1, int64_t N1,
                const double* x2_dN2, int64_t N2, int d, const double* l,
@@ -231,9 +262,11 @@ int gpf_set_profiling(gpf_ctx* ctx, int on);
  *  [12] factorisation wall ms (K build + diag + steps of all particle groups, which run
  *       on concurrent streams, so [0]/[3]/[6] may overlap)  [13] calls  [14] its flops
  *  [15] prediction V = U K_s kernel ms  [16] launches  [17] algorithmic flops
- *       (gpf_predict_cov: its V = U K_s and Sigma = K_ss - V^T V kernels, one launch each)
+ *       (gpf_predict_cov: its V = U K_s and Sigma = K_ss - V^T V kernels, one launch each;
+ *       gpf_chol_dense / gpf_posterior_draws: also the dense factorisation's launches and k_draws)
  *  [18] prediction cross-covariance ms  [19] launches  [20] algorithmic bytes
- *       (gpf_predict_cov: K_s and K_ss in one entry, and the mirror copy of Sigma's lower triangle)
+ *       (gpf_predict_cov: K_s and K_ss in one entry, and the mirror copy of Sigma's lower triangle;
+ *       gpf_chol_dense: the padding and mirror copy of the uploaded matrix)
  *  [21] probability-surface kernel ms  [22] launches  [23] algorithmic bytes
  *  [24] shader clock (MHz) the factor kernels held while they ran (every workgroup's span in
  *       s_memtime clocks over its span in the 100 MHz s_memrealtime clock; profiled batches only)
