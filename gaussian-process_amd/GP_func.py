@@ -52,6 +52,15 @@ def GP_cov(x_known, y_known, e_known, x_fit, lengths):
     return ctx.predict_cov(lengths, x_fit)
 
 
+def GP_linear(x_known, y_known, e_known, x_fit, lengths, weights):
+    """Linear functionals of the latent GP at x_fit (d, M) with the weights (R, M): (mean (R,),
+    cov (R, R)) = (A mu, A cov A^T) of GP_cov's posterior — region sums and averages
+    (gpfit.linear.region_weights), differences — without the M x M covariance: the query axis is
+    folded away on the device chunk by chunk (gpf_predict_linear), so M is not capped by it."""
+    from gpfit.linear import predict_linear
+    return predict_linear(x_known, y_known, e_known, x_fit, lengths, weights, method="stream")[:2]
+
+
 def GP_draws(x_known, y_known, e_known, x_fit, lengths, n_draws, seed=None, method="host"):
     """n_draws joint draws of the latent GP at x_fit: (n_draws, M), from N(GP_cov's mu, cov) by a
     Cholesky factor of cov + jitter I: method="host" takes it with NumPy from the copied-back cov

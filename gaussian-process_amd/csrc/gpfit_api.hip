@@ -26,6 +26,7 @@
 #include "gpf_objective.hip"
 #include "gpf_predict.hip"
 #include "gpf_postcov.hip"
+#include "gpf_linear.hip"
 #include "gpf_densechol.hip"
 #include "gpf_lmlgrad.hip"
 #include "gpf_probsurf.hip"
@@ -138,6 +139,10 @@ struct gpf_ctx {
   double *g_L = nullptr, *g_z = nullptr, *g_dr = nullptr, *g_u = nullptr;
   int64_t g_cols = 0, g_rows = 0, g_np = 0;
   int g_d = 0, g_nt = 0;
+  // gpf_predict_linear's buffers (LIN_* below), apart from all of the above and kept under the same
+  // rule: each at least l_cap[i] bytes
+  void* l_buf[16] = {};
+  size_t l_cap[16] = {};
   // gpf_chol_dense's matrix, factor and U_JJ strip (grow-only, kept under the same rule); the status
   // word of a dense factorisation sits behind its strip (dense_chol_strip_bytes)
   Scratch dc_a, dc_l, dc_u;
@@ -280,6 +285,14 @@ static void free_pdraw(gpf_ctx* c) {
   c->g_d = c->g_nt = 0;
 }
 
+static void free_plin(gpf_ctx* c) {
+  for (int i = 0; i < 16; ++i) {
+    hipFree(c->l_buf[i]);
+    c->l_buf[i] = nullptr;
+    c->l_cap[i] = 0;
+  }
+}
+
 static void free_dchol(gpf_ctx* c) {
   for (Scratch* s : {&c->dc_a, &c->dc_l, &c->dc_u}) s->release();
 }
@@ -287,6 +300,7 @@ static void free_dchol(gpf_ctx* c) {
 static void free_pred(gpf_ctx* c) {
   free_pcov(c);
   free_pdraw(c);
+  free_plin(c);
   free_dchol(c);
   hipFree(c->p_xf); hipFree(c->p_ks); hipFree(c->p_vsq); hipFree(c->p_mu); hipFree(c->p_sd); hipFree(c->p_vz);
   hipHostFree(c->p_hx); hipHostFree(c->p_hout);
@@ -1128,6 +1142,252 @@ int gpf_predict_cov(gpf_ctx* c, const double* ls, const double* xfit, int64_t M,
   }
   if (c->prof) harvest(c);
   if (pcov_bytes(c, (double)c->c_cols) > keep_bytes(knobs)) free_pcov(c);
+  return rc;
+}
+
+// ---- linear functionals of the posterior (gpf_linear.hip) ----
+// gpf_predict_linear's device buffers (gpf_ctx::l_buf)
+enum LinBuf {
+  LIN_WRAW = 0,  // the weights as given, R x M
+  LIN_WT,        // Wt = A^T, Mp x Rp, zero padded
+  LIN_G,         // G = K_ss Wt, Mp x Rp
+  LIN_XF,        // the query coordinates, d x Mp
+  LIN_BLK,       // one kernel block: K_s[:, c] (Np x Cc) or K_ss[c1, c2] (Cc x Cc)
+  LIN_B,         // B = K_s Wt, Np x Rp
+  LIN_V,         // V_A = U B, Np x Rp
+  LIN_Q,         // Q = Wt^T G = A K_ss A^T, Rp x Rp
+  LIN_COV,       // Q - V_A^T V_A, Rp x Rp
+  LIN_VSQ,       // k_predict_v's partials, nt x Rp each
+  LIN_VZ,
+  LIN_MU,        // (mean | k_predict_out's sd slot), 2 Rp
+  LIN_PART,      // the partial tiles of the product in flight
+  LIN_NBUF
+};
+static_assert(LIN_NBUF <= 16, "gpf_ctx::l_buf");
+
+// The shape of one gpf_predict_linear call: the padded sizes, the query points per pass and the bytes
+// of every buffer
+struct LinPlan {
+  int64_t Mp, Cc, Np;
+  int Rp, Rt, nt, d;
+  size_t bytes[LIN_NBUF];
+  double total;
+};
+
+static LinPlan lin_plan(const gpf_ctx* c, int64_t M, int R, int64_t Cc) {
+  LinPlan p{};
+  p.Np = c->Npad;
+  p.nt = c->nt;
+  p.d = c->d;
+  p.Mp = ((M + T - 1) / T) * T;
+  p.Rp = ((R + T - 1) / T) * T;
+  p.Rt = p.Rp / T;
+  p.Cc = std::min(Cc, p.Mp);
+  const size_t Mp = (size_t)p.Mp, Rp = (size_t)p.Rp, Np = (size_t)p.Np, C = (size_t)p.Cc;
+  const int ct = (int)(p.Cc / T), ntri = p.Rt * (p.Rt + 1) / 2;
+  // the partial tiles of the largest launch. A launch over `tiles` output tiles and dt depth tiles has
+  // at most min(dt, ceil(LIN_WG / tiles)) pieces (lin_pieces), so fewer than min(tiles dt, tiles +
+  // LIN_WG) partial tiles, which grows with both: bound each product at its largest pass (B's and G's
+  // at a full chunk, Q over Mp, V_A^T V_A over Np); a ragged last chunk needs no more
+  auto bound = [](size_t tiles, size_t dt) { return std::min(tiles * dt, tiles + (size_t)gpf::LIN_WG); };
+  size_t ptiles = bound((size_t)p.nt * p.Rt, ct);
+  ptiles = std::max(ptiles, bound((size_t)ct * p.Rt, ct));
+  ptiles = std::max(ptiles, bound(ntri, (size_t)(p.Mp / T)));
+  ptiles = std::max(ptiles, bound(ntri, p.nt));
+  p.bytes[LIN_WRAW] = (size_t)R * (size_t)M * 8;
+  p.bytes[LIN_WT] = p.bytes[LIN_G] = Mp * Rp * 8;
+  p.bytes[LIN_XF] = (size_t)p.d * Mp * 8;
+  p.bytes[LIN_BLK] = std::max(Np, C) * C * 8;
+  p.bytes[LIN_B] = p.bytes[LIN_V] = Np * Rp * 8;
+  p.bytes[LIN_Q] = p.bytes[LIN_COV] = Rp * Rp * 8;
+  p.bytes[LIN_VSQ] = p.bytes[LIN_VZ] = (size_t)p.nt * Rp * 8;
+  p.bytes[LIN_MU] = 2 * Rp * 8;
+  p.bytes[LIN_PART] = ptiles * gpf::LIN_TT * 8;
+  for (int i = 0; i < LIN_NBUF; ++i) p.total += (double)p.bytes[i];
+  return p;
+}
+
+static bool lin_fits_kept(const gpf_ctx* c, const LinPlan& p) {
+  for (int i = 0; i < LIN_NBUF; ++i)
+    if (p.bytes[i] > c->l_cap[i]) return false;
+  return true;
+}
+
+// One skinny product behind the stream: the partial tiles of `tiles` output tiles over dt depth
+// tiles (launch_parts queues k_lin_nn or k_lin_tn with the piece size it is given), then their
+// ordered sum into out (+ base, or base - sum with sgn = -1).
+extern "C++" template <typename F>
+static int lin_product(gpf_ctx* c, int tiles, int nct, bool tri, int dt, double flops, const double* base, double sgn,
+                       double* out, int64_t ldo, F launch_parts) {
+  int per;
+  const int pieces = gpf::lin_pieces(dt, tiles, &per);
+  double* part = (double*)c->l_buf[LIN_PART];
+  int rc = launch(c, PC_PRED, flops, [&] { launch_parts(dim3((unsigned)tiles, (unsigned)pieces), per, part); });
+  if (!rc)
+    rc = launch(c, PC_PRED, 0.0, [&] {
+      hipLaunchKernelGGL(gpf::k_lin_reduce, dim3((unsigned)tiles, 8), dim3(NTHR), 0, c->stream, nct, tri ? 1 : 0, pieces, part,
+                         base, sgn, out, ldo);
+    });
+  return rc;
+}
+
+int gpf_predict_linear(gpf_ctx* c, const double* ls, const double* xfit, int64_t M, const double* w, int R, int64_t chunk,
+                       double* mean, double* cov, double* prior) {
+  if (!c) return GPF_BAD_ARG;
+  if (c->N <= 0) return bad_arg(c, "gpf_predict_linear: call gpf_set_data first");
+  if (M < 0 || R < 0 || chunk < 0) return bad_arg(c, "gpf_predict_linear: M, R and chunk must be >= 0");
+  if (!ls) return bad_arg(c, "gpf_predict_linear: null length scales");
+  if (M > 0 && R > 0 && (!xfit || !w || !mean || !cov)) return bad_arg(c, "gpf_predict_linear: null buffer");
+  for (int k = 0; k < c->d; ++k)
+    if (!(ls[k] > 0.0) || !std::isfinite(ls[k])) return bad_arg(c, "gpf_predict_linear: length scales must be finite and > 0");
+  if (M > (int64_t)1 << 30) return bad_arg(c, "gpf_predict_linear: M > 2^30");
+  if (R > 1 << 14) return bad_arg(c, "gpf_predict_linear: R > 16384");
+  if (M == 0 || R == 0) return GPF_OK;
+  for (size_t i = 0, n = (size_t)R * (size_t)M; i < n; ++i)
+    if (!std::isfinite(w[i])) return bad_arg(c, "gpf_predict_linear: weights must be finite");
+  hipSetDevice(c->device);
+  if (c->K <= 0) c->K = 2;  // (as gpf_predict: the objective grid is not needed)
+  // the factorisation workspace first: a (re)allocation there frees the query buffers too
+  const Knobs knobs = Knobs::from_env();
+  if (int rw = ensure_work(c, 1, knobs)) return rw;
+  // query points per pass: the caller's, or gpf_predict's default, in whole tiles (the block's
+  // leading dimension and the byte offsets of the streamed panels stay well inside 32 bits)
+  int64_t Cc = std::min<int64_t>(chunk > 0 ? chunk : 16384, 65536);
+  Cc = ((Cc + T - 1) / T) * T;
+  LinPlan p = lin_plan(c, M, R, Cc);
+  if (!lin_fits_kept(c, p)) {
+    GPF_HIP(c, hipStreamSynchronize(c->stream));
+    free_plin(c);
+    size_t fr = 0, tot = 0;
+    GPF_HIP(c, hipMemGetInfo(&fr, &tot));
+    const double budget = 0.5 * (double)fr;
+    while (p.total > budget && p.Cc > T) {  // fewer query points per pass
+      Cc = std::max<int64_t>(T, ((p.Cc / 2 + T - 1) / T) * T);
+      p = lin_plan(c, M, R, Cc);
+    }
+    if (p.total > budget) {
+      int64_t fit = 0;  // the largest multiple of the tile that fits at this R (the bytes grow with M)
+      for (int64_t lo = 0, hi = p.Mp / T; lo < hi;) {
+        const int64_t mid = (lo + hi + 1) / 2;
+        if (lin_plan(c, mid * T, R, T).total <= budget) fit = mid * T, lo = mid; else hi = mid - 1;
+      }
+      c->err = "gpf_predict_linear: the weights, the coordinates and the operands for M=" + std::to_string(M) + ", R=" +
+               std::to_string(R) + " at N=" + std::to_string(c->N) + " need " + std::to_string((long long)(p.total / 1048576.0)) +
+               " MiB at 128 query points per pass, more than half of the free " + std::to_string((long long)(fr / 1048576)) +
+               " MiB of device memory; the largest M that fits at this R is " + std::to_string(fit);
+      return GPF_BAD_ARG;
+    }
+    for (int i = 0; i < LIN_NBUF; ++i) {
+      GPF_HIP(c, hipMalloc(&c->l_buf[i], p.bytes[i]));
+      c->l_cap[i] = p.bytes[i];
+    }
+  }
+  Cc = p.Cc;
+  const int64_t Np = p.Np, Mp = p.Mp;
+  const int Rp = p.Rp, Rt = p.Rt, nt = p.nt, d = p.d;
+  auto buf = [&](int i) { return (double*)c->l_buf[i]; };
+  double *wt = buf(LIN_WT), *G = buf(LIN_G), *xf = buf(LIN_XF), *blk = buf(LIN_BLK), *B = buf(LIN_B), *V = buf(LIN_V);
+  double *Q = buf(LIN_Q), *S = buf(LIN_COV), *mu = buf(LIN_MU);
+  hipStream_t st = c->stream;
+
+  // the length scales, the coordinates (leading dimension Mp) and the weights, then the factorisation
+  std::memcpy(c->h_ls, ls, (size_t)d * 8);
+  GPF_HIP(c, hipMemcpyAsync(c->d_ls, c->h_ls, (size_t)d * 8, hipMemcpyHostToDevice, st));
+  GPF_HIP(c, hipMemcpy2DAsync(xf, (size_t)Mp * 8, xfit, (size_t)M * 8, (size_t)M * 8, (size_t)d, hipMemcpyHostToDevice, st));
+  GPF_HIP(c, hipMemcpyAsync(buf(LIN_WRAW), w, (size_t)R * (size_t)M * 8, hipMemcpyHostToDevice, st));
+  int rc = launch(c, PC_PREDK, 8.0 * (double)Mp * Rp, [&] {
+    hipLaunchKernelGGL(gpf::k_lin_wt, dim3((unsigned)(Mp / 64), (unsigned)(Rp / 64)), dim3(NTHR), 0, st, R, M, buf(LIN_WRAW), wt, Rp);
+  });
+  if (!rc) rc = factor_single_async(c, nullptr, nullptr, knobs);
+
+  // B = K_s Wt, a chunk of query points per pass
+  for (int64_t s = 0; s < M && !rc; s += Cc) {
+    const int64_t m = std::min<int64_t>(Cc, M - s);
+    const int Cm = (int)(((m + T - 1) / T) * T);
+    rc = launch(c, PC_PREDK, 8.0 * (double)Np * Cm, [&] {
+      gpf::launch_cross_cov(st, (int)c->N, (int)m, (int)Np, Cm, d, c->d_x, (int)c->N, xf + s, (int)Mp, c->d_ls, blk, Cc);
+    });
+    if (rc) break;
+    const double* ws = wt + (size_t)s * Rp;
+    rc = lin_product(c, nt * Rt, Rt, false, Cm / T, 2.0 * (double)Np * Cm * Rp, s ? B : nullptr, 1.0, B, Rp,
+                     [&](dim3 grid, int per, double* part) {
+                       hipLaunchKernelGGL(gpf::k_lin_nn, grid, dim3(gpf::Geo<T>::NTH), 0, st, Rt, Cm / T, per, blk, (int)Cc, ws,
+                                          Rp, part);
+                     });
+  }
+  // V_A = U B with the mean's partials (sum over the row tiles of V_A^T z = B^T alpha = A mu)
+  const double vflops = 2.0 * T * T * (double)Rp * ((double)nt * (nt + 1) / 2) - (double)T * T * Rp * nt;
+  if (!rc)
+    rc = launch(c, PC_PRED, vflops, [&] {
+      hipLaunchKernelGGL(gpf::k_predict_v, dim3(Rt, nt), dim3(gpf::Geo<T>::NTH), 0, st, (int)Np, c->d_U, B, Rp, buf(LIN_VSQ),
+                         c->d_yb, buf(LIN_VZ), V);
+    });
+  if (!rc)
+    rc = launch(c, PC_LOSS, 0.0, [&] {
+      hipLaunchKernelGGL(gpf::k_predict_out, dim3((unsigned)((R + NTHR - 1) / NTHR)), dim3(NTHR), 0, st, nt, R, buf(LIN_VZ), Rp,
+                         buf(LIN_VSQ), mu, mu + Rp);
+    });
+  // G = K_ss Wt: the rows of chunk c1 over every chunk c2, one K_ss block at a time
+  for (int64_t s1 = 0; s1 < M && !rc; s1 += Cc) {
+    const int64_t m1 = std::min<int64_t>(Cc, M - s1);
+    const int C1 = (int)(((m1 + T - 1) / T) * T);
+    double* G1 = G + (size_t)s1 * Rp;
+    for (int64_t s2 = 0; s2 < M && !rc; s2 += Cc) {
+      const int64_t m2 = std::min<int64_t>(Cc, M - s2);
+      const int C2 = (int)(((m2 + T - 1) / T) * T);
+      rc = launch(c, PC_PREDK, 8.0 * (double)C1 * C2, [&] {
+        gpf::launch_cross_cov(st, (int)m1, (int)m2, C1, C2, d, xf + s1, (int)Mp, xf + s2, (int)Mp, c->d_ls, blk, Cc);
+        if (s1 == s2)
+          hipLaunchKernelGGL(gpf::k_lin_unit_diag, dim3((unsigned)((m1 + NTHR - 1) / NTHR)), dim3(NTHR), 0, st, (int)m1, blk, Cc);
+      });
+      if (rc) break;
+      const double* ws = wt + (size_t)s2 * Rp;
+      rc = lin_product(c, (C1 / T) * Rt, Rt, false, C2 / T, 2.0 * (double)C1 * C2 * Rp, s2 ? G1 : nullptr, 1.0, G1, Rp,
+                       [&](dim3 grid, int per, double* part) {
+                         hipLaunchKernelGGL(gpf::k_lin_nn, grid, dim3(gpf::Geo<T>::NTH), 0, st, Rt, C2 / T, per, blk, (int)Cc, ws,
+                                            Rp, part);
+                       });
+    }
+  }
+  // Q = Wt^T G (the prior covariance of the functionals) and Q - V_A^T V_A, lower tiles, then the mirror
+  // copies. (k_post_cov is not used on Q: it pins the diagonal to K_ss's 1.0, which is not Q's.)
+  const int ntri = Rt * (Rt + 1) / 2;
+  if (!rc)
+    rc = lin_product(c, ntri, Rt, true, (int)(Mp / T), 2.0 * T * T * (double)Mp * ntri, nullptr, 1.0, Q, Rp,
+                     [&](dim3 grid, int per, double* part) {
+                       hipLaunchKernelGGL(gpf::k_lin_tn, grid, dim3(gpf::Geo<T>::NTH), 0, st, (int)(Mp / T), per, wt, G, Rp, part);
+                     });
+  if (!rc)
+    rc = lin_product(c, ntri, Rt, true, nt, 2.0 * T * T * (double)Np * ntri, Q, -1.0, S, Rp,
+                     [&](dim3 grid, int per, double* part) {
+                       hipLaunchKernelGGL(gpf::k_lin_tn, grid, dim3(gpf::Geo<T>::NTH), 0, st, nt, per, V, V, Rp, part);
+                     });
+  const int nmb = (R + gpf::MIR_B - 1) / gpf::MIR_B;
+  if (!rc)
+    rc = launch(c, PC_PREDK, 16.0 * (double)R * R, [&] {
+      hipLaunchKernelGGL(gpf::k_mirror_lower, dim3((unsigned)(nmb * (nmb + 1) / 2)), dim3(NTHR), 0, st, R, Q, (int64_t)Rp);
+      hipLaunchKernelGGL(gpf::k_mirror_lower, dim3((unsigned)(nmb * (nmb + 1) / 2)), dim3(NTHR), 0, st, R, S, (int64_t)Rp);
+    });
+  if (hipStreamSynchronize(st) != hipSuccess && !rc) {
+    rc = GPF_HIP_ERROR;
+    c->err = "gpf_predict_linear: synchronisation failed";
+  }
+  // the factorisation's status before anything reaches the caller's buffers
+  if (!rc) rc = particle_status(c, 0);
+  if (!rc) {
+    const size_t row = (size_t)R * 8, pitch = (size_t)Rp * 8;
+    if (hipMemcpyAsync(mean, mu, row, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpy2DAsync(cov, row, S, pitch, row, (size_t)R, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        (prior && hipMemcpy2DAsync(prior, row, Q, pitch, row, (size_t)R, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+        hipStreamSynchronize(st) != hipSuccess) {
+      rc = GPF_HIP_ERROR;
+      c->err = "gpf_predict_linear: copy back failed";
+    }
+  }
+  if (c->prof) harvest(c);
+  double held = 0.0;
+  for (int i = 0; i < LIN_NBUF; ++i) held += (double)c->l_cap[i];
+  if (held > keep_bytes(knobs)) free_plin(c);
   return rc;
 }
 

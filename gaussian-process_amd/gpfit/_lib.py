@@ -37,6 +37,7 @@ SIGNATURES = {
     "gpf_eval_batch": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _dp, _dp, _dp, _ip]),
     "gpf_predict": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int64, ctypes.c_int64, _dp, _dp]),
     "gpf_predict_cov": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int64, _dp, _dp]),
+    "gpf_predict_linear": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int64, _dp, ctypes.c_int, ctypes.c_int64, _dp, _dp, _dp]),
     "gpf_chol_dense": (ctypes.c_int, [_vp, _dp, ctypes.c_int64, _dp, ctypes.c_int, _dp, _dp, _ip]),
     "gpf_posterior_draws": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int64, _dp, ctypes.c_int64, _dp, ctypes.c_int,
                                            _dp, _dp, _dp, _dp, _ip]),
@@ -294,6 +295,31 @@ class Context:
         mu, cov = np.empty(m), np.empty((m, m))
         self._check(self.lib.gpf_predict_cov(self._h, _ptr(ls), _ptr(xf), m, _ptr(mu), _ptr(cov)), "gpf_predict_cov")
         return mu, cov
+
+    def predict_linear(self, lengths, x_fit, weights, chunk=0, want_prior=False):
+        """Linear functionals of the latent posterior at x_fit (d, M) with the weights (R, M), one row
+        per functional (gpf_predict_linear): (mean (R,), cov (R, R)) = (A mu, A Sigma A^T) with
+        predict_cov's Sigma, without the M x M matrix: the query axis is folded away ``chunk`` points
+        per pass (rounded up to 128; 0: the library's default). With want_prior also the prior
+        covariance A K_ss A^T (R, R). cov and prior are exactly symmetric and not clipped. The same
+        chunk gives the same bits on every call; another chunk may differ in the last bits.
+        LinAlgError if the covariance of the training points is not positive definite, ValueError for
+        bad arguments or an M that does not fit the device at this R (the message names the largest)."""
+        ls, xf, w = _f64(lengths).reshape(-1), _f64(x_fit), _f64(weights)
+        if xf.ndim != 2:
+            raise ValueError("x_fit must be (d, M)")
+        if self.d and (xf.shape[0] != self.d or ls.shape[0] != self.d):
+            raise ValueError(f"x_fit must be ({self.d}, M) and lengths ({self.d},)")
+        m = xf.shape[1]
+        if w.ndim != 2 or w.shape[1] != m:
+            raise ValueError(f"weights must be (R, {m})")
+        r = w.shape[0]
+        mean, cov = np.empty(r), np.empty((r, r))
+        prior = np.empty((r, r)) if want_prior else None
+        rc = self.lib.gpf_predict_linear(self._h, _ptr(ls), _ptr(xf), m, _ptr(w), r, int(chunk), _ptr(mean), _ptr(cov),
+                                         _ptr(prior) if want_prior else None)
+        self._check(rc, "gpf_predict_linear")
+        return (mean, cov, prior) if want_prior else (mean, cov)
 
     def chol_dense(self, a, jitters=JITTERS):
         """Cholesky factor of the dense symmetric matrix a (n, n) on the device (gpf_chol_dense):

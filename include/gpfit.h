@@ -104,6 +104,40 @@ int gpf_predict(gpf_ctx* ctx, const double* ls, const double* xfit_dM,
 int gpf_predict_cov(gpf_ctx* ctx, const double* ls, const double* xfit_dM, int64_t M,
                     double* mu_M, double* cov_MM);
 
+/* R linear functionals of the latent posterior at the M query points xfit_dM (d, M), without the
+ * M x M covariance: with the weights w_RM (R, M) row-major, row r the weights of functional r,
+ *   mean_R[r] = sum_q w[r,q] mu_q                               (A mu)
+ *   cov_RR    = A K_ss A^T - V_A^T V_A, V_A = L^-1 (K_s A^T)    (A Sigma A^T, Sigma as gpf_predict_cov's)
+ *   prior_RR  = A K_ss A^T (nullable): the prior covariance of the functionals.
+ * The model is gpf_predict_cov's: K_ss = kernel_func(xfit, xfit, l) with the diagonal exactly 1.0, and
+ * cov_RR is not clipped. cov_RR and prior_RR are full R x R row-major matrices, both triangles
+ * written, exactly symmetric (the upper triangle is a copy of the lower).
+ * The query axis is chunked: `chunk` query points per pass, rounded up to 128 and capped at 65536;
+ * 0 means gpf_predict's default of 16384. Nothing of size M x M or Npad x M is allocated: K_s A^T
+ * (Npad x Rpad) is accumulated over the chunks and K_ss A^T (Mpad x Rpad) over pairs of chunks, one
+ * kernel block (max(Npad, chunk) x chunk) at a time. On the device for the call: the weights as given
+ * and transposed (R x M, Mpad x Rpad), K_ss A^T (Mpad x Rpad), the coordinates (d x Mpad), one kernel
+ * block, the Npad x Rpad and Rpad x Rpad operands and up to about 1024 + the output's tiles partial
+ * 128 x 128 tiles. If that exceeds half of the free device memory, chunk is halved until it fits; if
+ * it does not fit at chunk = 128 the call returns GPF_BAD_ARG and gpf_last_error names the largest M
+ * that fits at this R. The buffers are kept under GPF_PREDICT_KEEP_MB, apart from those of gpf_predict,
+ * gpf_predict_cov and gpf_posterior_draws: interleaved calls of those keep their bits.
+ * Repeating a call with the same chunk gives the same bits (every sum runs in a fixed order that the
+ * shapes alone decide; no floating-point atomics). Different chunk values change the order of the
+ * sums over the query axis and may differ in the last bits.
+ * GPF_NOT_PD as gpf_predict_cov: the outputs are then untouched. GPF_BAD_ARG, before any device
+ * work: null ctx, no data set, M < 0, R < 0 or chunk < 0, null ls, a null buffer with M > 0 and R > 0
+ * (prior_RR may be null), a length scale that is not finite and > 0, a non-finite weight, M > 2^30 or
+ * R > 16384. M == 0 or R == 0 returns GPF_OK and writes nothing.
+ * Measured on one MI355X at N=4096, d=3, R=128 (profiles/predict_linear/bench.json): M=4096 about
+ * 3 ms per call against about 29 ms for gpf_predict_cov followed by A Sigma A^T on the host;
+ * M=200000, which gpf_predict_cov cannot hold, about 250 ms per call at the default chunk and 1.1,
+ * 1.8 and 2.8 times that at chunk 8192, 4096 and 2048 (smaller chunks give the products shorter
+ * depth pieces and more launches). */
+int gpf_predict_linear(gpf_ctx* ctx, const double* ls, const double* xfit_dM, int64_t M,
+                       const double* w_RM, int R, int64_t chunk,
+                       double* mean_R, double* cov_RR, double* prior_RR);
+
 /* Cholesky factor of a dense symmetric host matrix on the device: tries A + jitters[t] I for
  * t = 0, 1, .. until one factorises. L_nn: n x n row-major, zeros above the diagonal.
  * Only A's lower triangle is read. A blocked left-looking factorisation on 128-tiles with FP64
@@ -263,10 +297,14 @@ int gpf_set_profiling(gpf_ctx* ctx, int on);
  *       on concurrent streams, so [0]/[3]/[6] may overlap)  [13] calls  [14] its flops
  *  [15] prediction V = U K_s kernel ms  [16] launches  [17] algorithmic flops
  *       (gpf_predict_cov: its V = U K_s and Sigma = K_ss - V^T V kernels, one launch each;
- *       gpf_chol_dense / gpf_posterior_draws: also the dense factorisation's launches and k_draws)
+ *       gpf_chol_dense / gpf_posterior_draws: also the dense factorisation's launches and k_draws;
+ *       gpf_predict_linear: its skinny products — a k_lin_nn or k_lin_tn launch with the product's
+ *       flops 2 rows depth Rpad, and the k_lin_reduce launch behind it with none — and k_predict_v)
  *  [18] prediction cross-covariance ms  [19] launches  [20] algorithmic bytes
  *       (gpf_predict_cov: K_s and K_ss in one entry, and the mirror copy of Sigma's lower triangle;
- *       gpf_chol_dense: the padding and mirror copy of the uploaded matrix)
+ *       gpf_chol_dense: the padding and mirror copy of the uploaded matrix;
+ *       gpf_predict_linear: one entry per kernel block built, 8 bytes per element, the transposed
+ *       copy of the weights and the two mirror copies)
  *  [21] probability-surface kernel ms  [22] launches  [23] algorithmic bytes
  *  [24] shader clock (MHz) the factor kernels held while they ran (every workgroup's span in
  *       s_memtime clocks over its span in the 100 MHz s_memrealtime clock; profiled batches only)
