@@ -61,6 +61,15 @@ def GP_linear(x_known, y_known, e_known, x_fit, lengths, weights):
     return predict_linear(x_known, y_known, e_known, x_fit, lengths, weights, method="stream")[:2]
 
 
+def GP_conditioned(x_known, y_known, e_known, x_fit, lengths, weights, values, noise):
+    """GP()'s (mu, sigma) at x_fit (d, M) after conditioning the latent GP on R measured linear
+    functionals as well: values[r] = sum_q weights[r, q] f(x_fit[:, q]) + N(0, noise[r]^2) — an
+    integrated value or bin averages of another experiment (gpfit.linear.region_weights builds the
+    weights of bins). Exact, streamed over the query axis (gpf_predict_conditioned): no M x M matrix."""
+    from gpfit.conditioned import predict_conditioned
+    return predict_conditioned(x_known, y_known, e_known, x_fit, lengths, weights, values, noise, method="stream")[:2]
+
+
 def GP_draws(x_known, y_known, e_known, x_fit, lengths, n_draws, seed=None, method="host"):
     """n_draws joint draws of the latent GP at x_fit: (n_draws, M), from N(GP_cov's mu, cov) by a
     Cholesky factor of cov + jitter I: method="host" takes it with NumPy from the copied-back cov

@@ -270,9 +270,9 @@ __device__ __forceinline__ void dl_row_offsets(int lane, uint32_t (&o)[4]) {
 // (8 row blocks) x one 16-column slab, so a k-step is 8 A reads, 1 B read and 8 MFMAs.
 // NS: LDS stages (2: double-buffered, the default; 3-4 for one-workgroup-per-CU launches, where
 // the next chunk's transfer has less time behind one chunk of MFMAs than two workgroups give it)
-// TN: A is given transposed, as a [k][r] row panel like the NN B panel: A(r,k) at Ap[k*ldb + r] (both
-// panels share the leading dimension ldb). The f64 16x16x4 A and B fragments are symmetric (lane l:
-// index l & 15, depth l >> 4), so A is staged and read exactly as the NN B side is: one k-row per 1 KiB
+// TN: A is given transposed, as a [k][r] row panel like the NN B panel: A(r,k) at Ap[k*lda + r] (its own
+// leading dimension: k_con_tn's panels differ, every other caller passes lda = ldb). The f64 16x16x4 A
+// and B fragments are symmetric (lane l: index l & 15, depth l >> 4), so A is staged and read exactly as the NN B side is: one k-row per 1 KiB
 // block, column pair cp of row k in slot cp ^ 8 (k % 4). Row block mi of an operand read then sits in
 // slot group mi ^ (lane >> 4) = (mi & 4) | ((mi & 3) ^ (lane >> 4)): one per-lane offset per mi & 3, the
 // upper row half and the k-step displacements immediates. acc += sum_k A(., k) B(k, .) with nothing
@@ -286,8 +286,9 @@ struct DenseRun {
   uint32_t la[4], lb[4];  // LDS read offsets (bytes) per k-step: A rows (TN: per row block mi & 3), B^T rows (!NN) / B (NN, [0] only)
   uint32_t ga[2], gb[2];  // global byte offsets of the two 1 KiB blocks per operand this wave fills
   int blk0;               // first block index of this wave
+  int ldat;               // TN: A's leading dimension (chunk displacement of the [k][r] panel)
 
-  __device__ __forceinline__ DenseRun(const Quad<128>& qd, int lda, int ldb, int wave) {
+  __device__ __forceinline__ DenseRun(const Quad<128>& qd, int lda, int ldb, int wave) : ldat(TN ? lda : 0) {
     const int lane = qd.lane, lr = lane & 15, lk = lane >> 4;
     if constexpr (TN) {
 #pragma unroll
@@ -307,7 +308,7 @@ struct DenseRun {
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int blk = blk0 + u, row = 8 * blk + (lane >> 3), kp = (lane & 7) ^ dl_sw(row);
-      ga[u] = TN ? 8u * (uint32_t)(blk * ldb + 2 * (lane ^ (8 * (blk & 3)))) : 8u * (uint32_t)(row * lda + 2 * kp);
+      ga[u] = TN ? 8u * (uint32_t)(blk * lda + 2 * (lane ^ (8 * (blk & 3)))) : 8u * (uint32_t)(row * lda + 2 * kp);
       gb[u] = NN ? 8u * (uint32_t)(blk * ldb + 2 * (lane ^ (8 * (blk & 3)))) : 8u * (uint32_t)(row * ldb + 2 * kp);
     }
   }
@@ -315,7 +316,7 @@ struct DenseRun {
   template <int BUF>
   __device__ __forceinline__ void issue(const double* Ap, const double* Bp, int ldb, int c, double* smem) const {
     // (uniform_ptr: a no-op where the chunk base is already scalar, as in every dense loop)
-    const char* Ac = uniform_ptr(TN ? (const char*)(Ap + (size_t)c * DL_KC * ldb) : (const char*)(Ap + c * DL_KC));
+    const char* Ac = uniform_ptr(TN ? (const char*)(Ap + (size_t)c * DL_KC * ldat) : (const char*)(Ap + c * DL_KC));
     const char* Bc = uniform_ptr(NN ? (const char*)(Bp + (size_t)c * DL_KC * ldb) : (const char*)(Bp + c * DL_KC));
     double* sbuf = smem + BUF * DL_BUF;
 #pragma unroll
@@ -420,7 +421,7 @@ struct DenseRun {
 // allocation of the dense loop); exactly the MFMAs tri_live admits are issued, so results are
 // bitwise those of per-block skipping. Every wave still passes one barrier per chunk.
 // BNT: the B panel loads non-temporal (a panel read once per launch; GPF_B_NT)
-// TN: A^T given as a [k][r] row panel with B's leading dimension (DenseRun); lda is not used
+// TN: A^T given as a [k][r] row panel with the leading dimension lda (DenseRun)
 template <bool NN, bool NEG = false, int TRI = TRI_NONE, int NS = 2, bool BNT = true, bool TN = false>
 __device__ __forceinline__ void gemm_stream_dl(Acc<128>& acc, const double* __restrict__ Ap, int lda, const double* __restrict__ Bp,
                                int ldb, int K, double* smem, const Quad<128>& qd) {

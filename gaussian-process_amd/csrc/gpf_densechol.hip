@@ -29,6 +29,8 @@
 // Every element's sum is seeded with the element of A and takes the block columns J = 0, 1, .. in
 // ascending order, each as one MFMA chain over ascending k continued from the stored value: one fixed
 // order whatever the schedule, no floating-point atomics, the same bits on every call.
+// Behind the factorisation: the transposed inverse of the factor from the same strip (k_dc_inv_*,
+// gpf_predict_conditioned; below, before k_draws).
 #pragma once
 #include "gpf_common.hip"
 #include "gpf_diag.hip"
@@ -163,6 +165,57 @@ __global__ __launch_bounds__(DNTH, 4) void k_dc_trail(int J, int m, double* __re
     gemm_stream_dl<false, true, TRI_NONE, 2, false>(acc, Lij, ld, L + (size_t)K * T * l + (size_t)J * T, ld, T, smem, qd);
     acc.store(qd, Cik, l);
   }
+}
+
+// ---- the transposed inverse of a dense factor: Xt = L^-T (gpf_predict_conditioned's Lh^-T) ----
+// Blocked forward substitution over the block rows I = 0, 1, .. of X = L^-1, written for the transpose
+// (upper tiles (J, I), J <= I, of Xt; the tiles below the diagonal are not touched: the caller zeroes
+// the buffer) so that a product with L^-T reads it as a [k][c] panel:
+//   Xt_II = U_II^T                                       k_dc_inv_diag, every block row at once
+//   Yt_JI = sum_{J <= K < I} Xt_JK L_IK^T   (J < I)      k_dc_inv_sum, into tile (J, I)
+//   Xt_JI = - Yt_JI U_II^T                               k_dc_inv_fin, tile (J, I) in place
+// with U_II = L_II^-1 from the strip the factorisation keeps. Two launches per block row I >= 1, ordered
+// by the stream alone (block row I reads the finished tiles of the block rows before it); every sum is
+// one MFMA chain over ascending k. L (nt 128 x ld, lower tiles), Xt (the same shape and ld), Us (128 x ld).
+
+// grid: (nt), NTHR threads
+__global__ __launch_bounds__(NTHR) void k_dc_inv_diag(const double* __restrict__ Us, double* __restrict__ Xt, int ld) {
+  const int I = blockIdx.x;
+  const size_t l = (size_t)ld;
+  const double* u = Us + (size_t)I * T;
+  double* x = Xt + (size_t)I * T * l + (size_t)I * T;
+  for (int idx = threadIdx.x; idx < T * T; idx += NTHR) {
+    const int r = idx >> 7, c = idx & (T - 1);
+    x[(size_t)r * l + c] = u[(size_t)c * l + r];
+  }
+}
+
+// grid: (I), DNTH threads: tile (J, I), J = blockIdx.x
+__global__ __launch_bounds__(DNTH, 4) void k_dc_inv_sum(int I, const double* __restrict__ L, double* __restrict__ Xt, int ld) {
+  __shared__ __attribute__((aligned(16))) double smem[DL_STAGE];
+  const int J = blockIdx.x;
+  const size_t l = (size_t)ld;
+  const Quad<T> qd;
+  Acc<T> acc;
+  acc.zero();
+  // A = row panel J of Xt from column 128 J ([r][k]); B^T = row panel I of L from the same column
+  gemm_stream_dl<false, false, TRI_NONE, 2, false>(acc, Xt + (size_t)J * T * l + (size_t)J * T, ld,
+                                                   L + (size_t)I * T * l + (size_t)J * T, ld, (I - J) * T, smem, qd);
+  acc.store(qd, Xt + (size_t)J * T * l + (size_t)I * T, l);
+}
+
+// grid: (I), DNTH threads: tile (J, I), J = blockIdx.x, read whole by this workgroup alone before it
+// is written (gemm_stream_dl ends behind its last transfer and a barrier)
+__global__ __launch_bounds__(DNTH, 4) void k_dc_inv_fin(int I, const double* __restrict__ Us, double* __restrict__ Xt, int ld) {
+  __shared__ __attribute__((aligned(16))) double smem[DL_STAGE];
+  const int J = blockIdx.x;
+  const size_t l = (size_t)ld;
+  const Quad<T> qd;
+  double* t = Xt + (size_t)J * T * l + (size_t)I * T;
+  Acc<T> acc;
+  acc.zero();
+  gemm_stream_dl<false, true, TRI_NONE, 2, false>(acc, t, ld, Us + (size_t)I * T, ld, T, smem, qd);  // - Yt U_II^T
+  acc.store(qd, t, l);
 }
 
 // draws[s, i] = mu[i] + sum_{j <= i} z[s, j] L[i, j]: tile (sample tile blockIdx.x, query tile I),

@@ -28,6 +28,7 @@
 #include "gpf_postcov.hip"
 #include "gpf_linear.hip"
 #include "gpf_densechol.hip"
+#include "gpf_conditioned.hip"
 #include "gpf_lmlgrad.hip"
 #include "gpf_probsurf.hip"
 #include "gpf_hull.hip"
@@ -143,6 +144,10 @@ struct gpf_ctx {
   // rule: each at least l_cap[i] bytes
   void* l_buf[16] = {};
   size_t l_cap[16] = {};
+  // gpf_predict_conditioned's buffers: a set like gpf_predict_linear's (LIN_*) and its own behind it
+  // (CON_*), apart from all of the above and kept under the same rule
+  void* n_buf[32] = {};
+  size_t n_cap[32] = {};
   // gpf_chol_dense's matrix, factor and U_JJ strip (grow-only, kept under the same rule); the status
   // word of a dense factorisation sits behind its strip (dense_chol_strip_bytes)
   Scratch dc_a, dc_l, dc_u;
@@ -293,6 +298,14 @@ static void free_plin(gpf_ctx* c) {
   }
 }
 
+static void free_pcon(gpf_ctx* c) {
+  for (int i = 0; i < 32; ++i) {
+    hipFree(c->n_buf[i]);
+    c->n_buf[i] = nullptr;
+    c->n_cap[i] = 0;
+  }
+}
+
 static void free_dchol(gpf_ctx* c) {
   for (Scratch* s : {&c->dc_a, &c->dc_l, &c->dc_u}) s->release();
 }
@@ -301,6 +314,7 @@ static void free_pred(gpf_ctx* c) {
   free_pcov(c);
   free_pdraw(c);
   free_plin(c);
+  free_pcon(c);
   free_dchol(c);
   hipFree(c->p_xf); hipFree(c->p_ks); hipFree(c->p_vsq); hipFree(c->p_mu); hipFree(c->p_sd); hipFree(c->p_vz);
   hipHostFree(c->p_hx); hipHostFree(c->p_hout);
@@ -1214,19 +1228,115 @@ static bool lin_fits_kept(const gpf_ctx* c, const LinPlan& p) {
 }
 
 // One skinny product behind the stream: the partial tiles of `tiles` output tiles over dt depth
-// tiles (launch_parts queues k_lin_nn or k_lin_tn with the piece size it is given), then their
-// ordered sum into out (+ base, or base - sum with sgn = -1).
+// tiles (launch_parts queues k_lin_nn, k_lin_tn or k_con_tn with the piece size it is given) into
+// part (the call's LIN_PART buffer), then their ordered sum into out (+ base, or base - sum with
+// sgn = -1).
 extern "C++" template <typename F>
-static int lin_product(gpf_ctx* c, int tiles, int nct, bool tri, int dt, double flops, const double* base, double sgn,
-                       double* out, int64_t ldo, F launch_parts) {
+static int lin_product(gpf_ctx* c, double* part, int tiles, int nct, bool tri, int dt, double flops, const double* base,
+                       double sgn, double* out, int64_t ldo, F launch_parts) {
   int per;
   const int pieces = gpf::lin_pieces(dt, tiles, &per);
-  double* part = (double*)c->l_buf[LIN_PART];
   int rc = launch(c, PC_PRED, flops, [&] { launch_parts(dim3((unsigned)tiles, (unsigned)pieces), per, part); });
   if (!rc)
     rc = launch(c, PC_PRED, 0.0, [&] {
       hipLaunchKernelGGL(gpf::k_lin_reduce, dim3((unsigned)tiles, 8), dim3(NTHR), 0, c->stream, nct, tri ? 1 : 0, pieces, part,
                          base, sgn, out, ldo);
+    });
+  return rc;
+}
+
+// gpf_predict_linear's device pipeline for the plan p, queued on the context's stream over the buffer
+// set bufs (LIN_*; sized by p): the uploads, Wt, the single-particle factorisation, B = K_s Wt, V_A
+// with the mean, G = K_ss Wt, Q and S = Q - V_A^T V_A and the two mirror copies. Leaves A mu in
+// LIN_MU, S in LIN_COV, Q in LIN_Q and B, V_A, G, Wt and the coordinates where they are.
+// gpf_predict_conditioned runs the same launches in the same order over its own buffers, so its
+// functionals are bitwise gpf_predict_linear's.
+static int lin_enqueue(gpf_ctx* c, const Knobs& knobs, void* const* bufs, const LinPlan& p, const double* ls,
+                       const double* xfit, int64_t M, const double* w, int R) {
+  const int64_t Cc = p.Cc, Np = p.Np, Mp = p.Mp;
+  const int Rp = p.Rp, Rt = p.Rt, nt = p.nt, d = p.d;
+  auto buf = [&](int i) { return (double*)bufs[i]; };
+  double *wt = buf(LIN_WT), *G = buf(LIN_G), *xf = buf(LIN_XF), *blk = buf(LIN_BLK), *B = buf(LIN_B), *V = buf(LIN_V);
+  double *Q = buf(LIN_Q), *S = buf(LIN_COV), *mu = buf(LIN_MU), *pt = buf(LIN_PART);
+  hipStream_t st = c->stream;
+
+  // the length scales, the coordinates (leading dimension Mp) and the weights, then the factorisation
+  std::memcpy(c->h_ls, ls, (size_t)d * 8);
+  GPF_HIP(c, hipMemcpyAsync(c->d_ls, c->h_ls, (size_t)d * 8, hipMemcpyHostToDevice, st));
+  GPF_HIP(c, hipMemcpy2DAsync(xf, (size_t)Mp * 8, xfit, (size_t)M * 8, (size_t)M * 8, (size_t)d, hipMemcpyHostToDevice, st));
+  GPF_HIP(c, hipMemcpyAsync(buf(LIN_WRAW), w, (size_t)R * (size_t)M * 8, hipMemcpyHostToDevice, st));
+  int rc = launch(c, PC_PREDK, 8.0 * (double)Mp * Rp, [&] {
+    hipLaunchKernelGGL(gpf::k_lin_wt, dim3((unsigned)(Mp / 64), (unsigned)(Rp / 64)), dim3(NTHR), 0, st, R, M, buf(LIN_WRAW), wt, Rp);
+  });
+  if (!rc) rc = factor_single_async(c, nullptr, nullptr, knobs);
+
+  // B = K_s Wt, a chunk of query points per pass
+  for (int64_t s = 0; s < M && !rc; s += Cc) {
+    const int64_t m = std::min<int64_t>(Cc, M - s);
+    const int Cm = (int)(((m + T - 1) / T) * T);
+    rc = launch(c, PC_PREDK, 8.0 * (double)Np * Cm, [&] {
+      gpf::launch_cross_cov(st, (int)c->N, (int)m, (int)Np, Cm, d, c->d_x, (int)c->N, xf + s, (int)Mp, c->d_ls, blk, Cc);
+    });
+    if (rc) break;
+    const double* ws = wt + (size_t)s * Rp;
+    rc = lin_product(c, pt, nt * Rt, Rt, false, Cm / T, 2.0 * (double)Np * Cm * Rp, s ? B : nullptr, 1.0, B, Rp,
+                     [&](dim3 grid, int per, double* part) {
+                       hipLaunchKernelGGL(gpf::k_lin_nn, grid, dim3(gpf::Geo<T>::NTH), 0, st, Rt, Cm / T, per, blk, (int)Cc, ws,
+                                          Rp, part);
+                     });
+  }
+  // V_A = U B with the mean's partials (sum over the row tiles of V_A^T z = B^T alpha = A mu)
+  const double vflops = 2.0 * T * T * (double)Rp * ((double)nt * (nt + 1) / 2) - (double)T * T * Rp * nt;
+  if (!rc)
+    rc = launch(c, PC_PRED, vflops, [&] {
+      hipLaunchKernelGGL(gpf::k_predict_v, dim3(Rt, nt), dim3(gpf::Geo<T>::NTH), 0, st, (int)Np, c->d_U, B, Rp, buf(LIN_VSQ),
+                         c->d_yb, buf(LIN_VZ), V);
+    });
+  if (!rc)
+    rc = launch(c, PC_LOSS, 0.0, [&] {
+      hipLaunchKernelGGL(gpf::k_predict_out, dim3((unsigned)((R + NTHR - 1) / NTHR)), dim3(NTHR), 0, st, nt, R, buf(LIN_VZ), Rp,
+                         buf(LIN_VSQ), mu, mu + Rp);
+    });
+  // G = K_ss Wt: the rows of chunk c1 over every chunk c2, one K_ss block at a time
+  for (int64_t s1 = 0; s1 < M && !rc; s1 += Cc) {
+    const int64_t m1 = std::min<int64_t>(Cc, M - s1);
+    const int C1 = (int)(((m1 + T - 1) / T) * T);
+    double* G1 = G + (size_t)s1 * Rp;
+    for (int64_t s2 = 0; s2 < M && !rc; s2 += Cc) {
+      const int64_t m2 = std::min<int64_t>(Cc, M - s2);
+      const int C2 = (int)(((m2 + T - 1) / T) * T);
+      rc = launch(c, PC_PREDK, 8.0 * (double)C1 * C2, [&] {
+        gpf::launch_cross_cov(st, (int)m1, (int)m2, C1, C2, d, xf + s1, (int)Mp, xf + s2, (int)Mp, c->d_ls, blk, Cc);
+        if (s1 == s2)
+          hipLaunchKernelGGL(gpf::k_lin_unit_diag, dim3((unsigned)((m1 + NTHR - 1) / NTHR)), dim3(NTHR), 0, st, (int)m1, blk, Cc);
+      });
+      if (rc) break;
+      const double* ws = wt + (size_t)s2 * Rp;
+      rc = lin_product(c, pt, (C1 / T) * Rt, Rt, false, C2 / T, 2.0 * (double)C1 * C2 * Rp, s2 ? G1 : nullptr, 1.0, G1, Rp,
+                       [&](dim3 grid, int per, double* part) {
+                         hipLaunchKernelGGL(gpf::k_lin_nn, grid, dim3(gpf::Geo<T>::NTH), 0, st, Rt, C2 / T, per, blk, (int)Cc, ws,
+                                            Rp, part);
+                       });
+    }
+  }
+  // Q = Wt^T G (the prior covariance of the functionals) and Q - V_A^T V_A, lower tiles, then the mirror
+  // copies. (k_post_cov is not used on Q: it pins the diagonal to K_ss's 1.0, which is not Q's.)
+  const int ntri = Rt * (Rt + 1) / 2;
+  if (!rc)
+    rc = lin_product(c, pt, ntri, Rt, true, (int)(Mp / T), 2.0 * T * T * (double)Mp * ntri, nullptr, 1.0, Q, Rp,
+                     [&](dim3 grid, int per, double* part) {
+                       hipLaunchKernelGGL(gpf::k_lin_tn, grid, dim3(gpf::Geo<T>::NTH), 0, st, (int)(Mp / T), per, wt, G, Rp, part);
+                     });
+  if (!rc)
+    rc = lin_product(c, pt, ntri, Rt, true, nt, 2.0 * T * T * (double)Np * ntri, Q, -1.0, S, Rp,
+                     [&](dim3 grid, int per, double* part) {
+                       hipLaunchKernelGGL(gpf::k_lin_tn, grid, dim3(gpf::Geo<T>::NTH), 0, st, nt, per, V, V, Rp, part);
+                     });
+  const int nmb = (R + gpf::MIR_B - 1) / gpf::MIR_B;
+  if (!rc)
+    rc = launch(c, PC_PREDK, 16.0 * (double)R * R, [&] {
+      hipLaunchKernelGGL(gpf::k_mirror_lower, dim3((unsigned)(nmb * (nmb + 1) / 2)), dim3(NTHR), 0, st, R, Q, (int64_t)Rp);
+      hipLaunchKernelGGL(gpf::k_mirror_lower, dim3((unsigned)(nmb * (nmb + 1) / 2)), dim3(NTHR), 0, st, R, S, (int64_t)Rp);
     });
   return rc;
 }
@@ -1282,92 +1392,10 @@ int gpf_predict_linear(gpf_ctx* c, const double* ls, const double* xfit, int64_t
       c->l_cap[i] = p.bytes[i];
     }
   }
-  Cc = p.Cc;
-  const int64_t Np = p.Np, Mp = p.Mp;
-  const int Rp = p.Rp, Rt = p.Rt, nt = p.nt, d = p.d;
-  auto buf = [&](int i) { return (double*)c->l_buf[i]; };
-  double *wt = buf(LIN_WT), *G = buf(LIN_G), *xf = buf(LIN_XF), *blk = buf(LIN_BLK), *B = buf(LIN_B), *V = buf(LIN_V);
-  double *Q = buf(LIN_Q), *S = buf(LIN_COV), *mu = buf(LIN_MU);
+  const int Rp = p.Rp;
+  double *Q = (double*)c->l_buf[LIN_Q], *S = (double*)c->l_buf[LIN_COV], *mu = (double*)c->l_buf[LIN_MU];
   hipStream_t st = c->stream;
-
-  // the length scales, the coordinates (leading dimension Mp) and the weights, then the factorisation
-  std::memcpy(c->h_ls, ls, (size_t)d * 8);
-  GPF_HIP(c, hipMemcpyAsync(c->d_ls, c->h_ls, (size_t)d * 8, hipMemcpyHostToDevice, st));
-  GPF_HIP(c, hipMemcpy2DAsync(xf, (size_t)Mp * 8, xfit, (size_t)M * 8, (size_t)M * 8, (size_t)d, hipMemcpyHostToDevice, st));
-  GPF_HIP(c, hipMemcpyAsync(buf(LIN_WRAW), w, (size_t)R * (size_t)M * 8, hipMemcpyHostToDevice, st));
-  int rc = launch(c, PC_PREDK, 8.0 * (double)Mp * Rp, [&] {
-    hipLaunchKernelGGL(gpf::k_lin_wt, dim3((unsigned)(Mp / 64), (unsigned)(Rp / 64)), dim3(NTHR), 0, st, R, M, buf(LIN_WRAW), wt, Rp);
-  });
-  if (!rc) rc = factor_single_async(c, nullptr, nullptr, knobs);
-
-  // B = K_s Wt, a chunk of query points per pass
-  for (int64_t s = 0; s < M && !rc; s += Cc) {
-    const int64_t m = std::min<int64_t>(Cc, M - s);
-    const int Cm = (int)(((m + T - 1) / T) * T);
-    rc = launch(c, PC_PREDK, 8.0 * (double)Np * Cm, [&] {
-      gpf::launch_cross_cov(st, (int)c->N, (int)m, (int)Np, Cm, d, c->d_x, (int)c->N, xf + s, (int)Mp, c->d_ls, blk, Cc);
-    });
-    if (rc) break;
-    const double* ws = wt + (size_t)s * Rp;
-    rc = lin_product(c, nt * Rt, Rt, false, Cm / T, 2.0 * (double)Np * Cm * Rp, s ? B : nullptr, 1.0, B, Rp,
-                     [&](dim3 grid, int per, double* part) {
-                       hipLaunchKernelGGL(gpf::k_lin_nn, grid, dim3(gpf::Geo<T>::NTH), 0, st, Rt, Cm / T, per, blk, (int)Cc, ws,
-                                          Rp, part);
-                     });
-  }
-  // V_A = U B with the mean's partials (sum over the row tiles of V_A^T z = B^T alpha = A mu)
-  const double vflops = 2.0 * T * T * (double)Rp * ((double)nt * (nt + 1) / 2) - (double)T * T * Rp * nt;
-  if (!rc)
-    rc = launch(c, PC_PRED, vflops, [&] {
-      hipLaunchKernelGGL(gpf::k_predict_v, dim3(Rt, nt), dim3(gpf::Geo<T>::NTH), 0, st, (int)Np, c->d_U, B, Rp, buf(LIN_VSQ),
-                         c->d_yb, buf(LIN_VZ), V);
-    });
-  if (!rc)
-    rc = launch(c, PC_LOSS, 0.0, [&] {
-      hipLaunchKernelGGL(gpf::k_predict_out, dim3((unsigned)((R + NTHR - 1) / NTHR)), dim3(NTHR), 0, st, nt, R, buf(LIN_VZ), Rp,
-                         buf(LIN_VSQ), mu, mu + Rp);
-    });
-  // G = K_ss Wt: the rows of chunk c1 over every chunk c2, one K_ss block at a time
-  for (int64_t s1 = 0; s1 < M && !rc; s1 += Cc) {
-    const int64_t m1 = std::min<int64_t>(Cc, M - s1);
-    const int C1 = (int)(((m1 + T - 1) / T) * T);
-    double* G1 = G + (size_t)s1 * Rp;
-    for (int64_t s2 = 0; s2 < M && !rc; s2 += Cc) {
-      const int64_t m2 = std::min<int64_t>(Cc, M - s2);
-      const int C2 = (int)(((m2 + T - 1) / T) * T);
-      rc = launch(c, PC_PREDK, 8.0 * (double)C1 * C2, [&] {
-        gpf::launch_cross_cov(st, (int)m1, (int)m2, C1, C2, d, xf + s1, (int)Mp, xf + s2, (int)Mp, c->d_ls, blk, Cc);
-        if (s1 == s2)
-          hipLaunchKernelGGL(gpf::k_lin_unit_diag, dim3((unsigned)((m1 + NTHR - 1) / NTHR)), dim3(NTHR), 0, st, (int)m1, blk, Cc);
-      });
-      if (rc) break;
-      const double* ws = wt + (size_t)s2 * Rp;
-      rc = lin_product(c, (C1 / T) * Rt, Rt, false, C2 / T, 2.0 * (double)C1 * C2 * Rp, s2 ? G1 : nullptr, 1.0, G1, Rp,
-                       [&](dim3 grid, int per, double* part) {
-                         hipLaunchKernelGGL(gpf::k_lin_nn, grid, dim3(gpf::Geo<T>::NTH), 0, st, Rt, C2 / T, per, blk, (int)Cc, ws,
-                                            Rp, part);
-                       });
-    }
-  }
-  // Q = Wt^T G (the prior covariance of the functionals) and Q - V_A^T V_A, lower tiles, then the mirror
-  // copies. (k_post_cov is not used on Q: it pins the diagonal to K_ss's 1.0, which is not Q's.)
-  const int ntri = Rt * (Rt + 1) / 2;
-  if (!rc)
-    rc = lin_product(c, ntri, Rt, true, (int)(Mp / T), 2.0 * T * T * (double)Mp * ntri, nullptr, 1.0, Q, Rp,
-                     [&](dim3 grid, int per, double* part) {
-                       hipLaunchKernelGGL(gpf::k_lin_tn, grid, dim3(gpf::Geo<T>::NTH), 0, st, (int)(Mp / T), per, wt, G, Rp, part);
-                     });
-  if (!rc)
-    rc = lin_product(c, ntri, Rt, true, nt, 2.0 * T * T * (double)Np * ntri, Q, -1.0, S, Rp,
-                     [&](dim3 grid, int per, double* part) {
-                       hipLaunchKernelGGL(gpf::k_lin_tn, grid, dim3(gpf::Geo<T>::NTH), 0, st, nt, per, V, V, Rp, part);
-                     });
-  const int nmb = (R + gpf::MIR_B - 1) / gpf::MIR_B;
-  if (!rc)
-    rc = launch(c, PC_PREDK, 16.0 * (double)R * R, [&] {
-      hipLaunchKernelGGL(gpf::k_mirror_lower, dim3((unsigned)(nmb * (nmb + 1) / 2)), dim3(NTHR), 0, st, R, Q, (int64_t)Rp);
-      hipLaunchKernelGGL(gpf::k_mirror_lower, dim3((unsigned)(nmb * (nmb + 1) / 2)), dim3(NTHR), 0, st, R, S, (int64_t)Rp);
-    });
+  int rc = lin_enqueue(c, knobs, c->l_buf, p, ls, xfit, M, w, R);
   if (hipStreamSynchronize(st) != hipSuccess && !rc) {
     rc = GPF_HIP_ERROR;
     c->err = "gpf_predict_linear: synchronisation failed";
@@ -1636,6 +1664,232 @@ int gpf_posterior_draws(gpf_ctx* c, const double* ls, const double* xfit, int64_
   hipStreamSynchronize(c->stream);
   if (c->prof) harvest(c);
   if (pdraw_bytes(c, (double)c->g_cols, (double)c->g_rows) > keep_bytes(knobs)) free_pdraw(c);
+  return rc;
+}
+
+// ---- the posterior conditioned on measured linear functionals (gpf_conditioned.hip) ----
+// gpf_predict_conditioned's device buffers (gpf_ctx::n_buf): the LIN_* set first, then its own
+enum ConBuf {
+  CON_W2 = LIN_NBUF,  // W2 = U^T V_A = Kn^-1 K_s A^T, Np x Rp
+  CON_H,              // H = A Sigma A^T + diag(s^2), Rp x Rp, identity padding
+  CON_LH,             // its factor Lh, lower tiles
+  CON_STRIP,          // the dense factorisation's U_JJ strip (dense_chol_strip_bytes)
+  CON_XT,             // Lh^-T, upper tiles, zero below
+  CON_C,              // C = Sigma A^T of the chunk in flight, Cc x Rp
+  CON_E,              // E = C Lh^-T of the chunk in flight, Cc x Rp
+  CON_G,              // (d = b - A mu | g = Lh^-1 d | chi2), 2 Rp + 1
+  CON_BS,             // (b | s), 2 Rp
+  CON_VSQ,            // k_predict_vsq's partials of the chunk in flight, nt x Cc each
+  CON_VZ,
+  CON_OUT,            // (mu' | sd'), Mp each
+  CON_NBUF
+};
+static_assert(CON_NBUF <= 32, "gpf_ctx::n_buf");
+
+struct ConPlan {
+  LinPlan lin;  // (its LIN_PART also holds the partial tiles of this call's own products)
+  size_t bytes[CON_NBUF];
+  double total;
+};
+
+static ConPlan con_plan(const gpf_ctx* c, int64_t M, int R, int64_t Cc) {
+  ConPlan q{};
+  q.lin = lin_plan(c, M, R, Cc);
+  const LinPlan& p = q.lin;
+  const size_t Mp = (size_t)p.Mp, Rp = (size_t)p.Rp, Np = (size_t)p.Np, C = (size_t)p.Cc;
+  const size_t ct = C / T;
+  // the partial tiles of W2 (nt Rt tiles, depth nt), C (ct Rt tiles, depth nt) and E (ct Rt tiles, depth Rt)
+  auto bound = [](size_t tiles, size_t dt) { return std::min(tiles * dt, tiles + (size_t)gpf::LIN_WG); };
+  size_t ptiles = std::max(bound((size_t)p.nt * p.Rt, p.nt), std::max(bound(ct * p.Rt, p.nt), bound(ct * p.Rt, p.Rt)));
+  for (int i = 0; i < LIN_NBUF; ++i) q.bytes[i] = p.bytes[i];
+  q.bytes[LIN_PART] = std::max(q.bytes[LIN_PART], ptiles * gpf::LIN_TT * 8);
+  q.bytes[CON_W2] = Np * Rp * 8;
+  q.bytes[CON_H] = q.bytes[CON_LH] = q.bytes[CON_XT] = Rp * Rp * 8;
+  q.bytes[CON_STRIP] = dense_chol_strip_bytes((int64_t)Rp);
+  q.bytes[CON_C] = q.bytes[CON_E] = C * Rp * 8;
+  q.bytes[CON_G] = (2 * Rp + 1) * 8;
+  q.bytes[CON_BS] = 2 * Rp * 8;
+  q.bytes[CON_VSQ] = q.bytes[CON_VZ] = (size_t)p.nt * C * 8;
+  q.bytes[CON_OUT] = 2 * Mp * 8;
+  for (int i = 0; i < CON_NBUF; ++i) q.total += (double)q.bytes[i];
+  return q;
+}
+
+int gpf_predict_conditioned(gpf_ctx* c, const double* ls, const double* xfit, int64_t M, const double* w, int R,
+                            const double* b, const double* sv, int64_t chunk, double* mu_out, double* sd_out, double* fmean,
+                            double* fcov, double* chi2) {
+  if (!c) return GPF_BAD_ARG;
+  // (gpf_predict_linear's checks, then this call's own)
+  if (c->N <= 0) return bad_arg(c, "gpf_predict_conditioned: call gpf_set_data first");
+  if (M < 0 || R < 0 || chunk < 0) return bad_arg(c, "gpf_predict_conditioned: M, R and chunk must be >= 0");
+  if (!ls) return bad_arg(c, "gpf_predict_conditioned: null length scales");
+  if (M > 0 && R > 0 && (!xfit || !w || !b || !sv || !mu_out || !sd_out)) return bad_arg(c, "gpf_predict_conditioned: null buffer");
+  for (int k = 0; k < c->d; ++k)
+    if (!(ls[k] > 0.0) || !std::isfinite(ls[k]))
+      return bad_arg(c, "gpf_predict_conditioned: length scales must be finite and > 0");
+  if (M > (int64_t)1 << 30) return bad_arg(c, "gpf_predict_conditioned: M > 2^30");
+  if (R > 1024) return bad_arg(c, "gpf_predict_conditioned: R > 1024 (larger R is not built yet)");
+  if (M == 0 || R == 0) return GPF_OK;
+  for (size_t i = 0, n = (size_t)R * (size_t)M; i < n; ++i)
+    if (!std::isfinite(w[i])) return bad_arg(c, "gpf_predict_conditioned: weights must be finite");
+  for (int r = 0; r < R; ++r) {
+    if (!std::isfinite(b[r])) return bad_arg(c, "gpf_predict_conditioned: the measured values must be finite");
+    if (!(sv[r] >= 0.0) || !std::isfinite(sv[r]))
+      return bad_arg(c, "gpf_predict_conditioned: the standard errors must be finite and >= 0");
+  }
+  hipSetDevice(c->device);
+  if (c->K <= 0) c->K = 2;  // (as gpf_predict: the objective grid is not needed)
+  // the factorisation workspace first: a (re)allocation there frees the query buffers too
+  const Knobs knobs = Knobs::from_env();
+  if (int rw = ensure_work(c, 1, knobs)) return rw;
+  int64_t Cc = std::min<int64_t>(chunk > 0 ? chunk : 16384, 65536);  // (as gpf_predict_linear)
+  Cc = ((Cc + T - 1) / T) * T;
+  ConPlan q = con_plan(c, M, R, Cc);
+  bool fits = true;
+  for (int i = 0; i < CON_NBUF; ++i) fits = fits && q.bytes[i] <= c->n_cap[i];
+  if (!fits) {
+    GPF_HIP(c, hipStreamSynchronize(c->stream));
+    free_pcon(c);
+    size_t fr = 0, tot = 0;
+    GPF_HIP(c, hipMemGetInfo(&fr, &tot));
+    const double budget = 0.5 * (double)fr;
+    while (q.total > budget && q.lin.Cc > T) {  // fewer query points per pass
+      Cc = std::max<int64_t>(T, ((q.lin.Cc / 2 + T - 1) / T) * T);
+      q = con_plan(c, M, R, Cc);
+    }
+    if (q.total > budget) {
+      int64_t fit = 0;  // the largest multiple of the tile that fits at this R (the bytes grow with M)
+      for (int64_t lo = 0, hi = q.lin.Mp / T; lo < hi;) {
+        const int64_t mid = (lo + hi + 1) / 2;
+        if (con_plan(c, mid * T, R, T).total <= budget) fit = mid * T, lo = mid; else hi = mid - 1;
+      }
+      c->err = "gpf_predict_conditioned: the weights, the coordinates and the operands for M=" + std::to_string(M) + ", R=" +
+               std::to_string(R) + " at N=" + std::to_string(c->N) + " need " + std::to_string((long long)(q.total / 1048576.0)) +
+               " MiB at 128 query points per pass, more than half of the free " + std::to_string((long long)(fr / 1048576)) +
+               " MiB of device memory; the largest M that fits at this R is " + std::to_string(fit);
+      return GPF_BAD_ARG;
+    }
+    for (int i = 0; i < CON_NBUF; ++i) {
+      GPF_HIP(c, hipMalloc(&c->n_buf[i], q.bytes[i]));
+      c->n_cap[i] = q.bytes[i];
+    }
+  }
+  const LinPlan& p = q.lin;
+  Cc = p.Cc;
+  const int64_t Np = p.Np, Mp = p.Mp;
+  const int Rp = p.Rp, Rt = p.Rt, nt = p.nt, d = p.d;
+  auto buf = [&](int i) { return (double*)c->n_buf[i]; };
+  double *G = buf(LIN_G), *xf = buf(LIN_XF), *blk = buf(LIN_BLK), *V = buf(LIN_V), *S = buf(LIN_COV), *amu = buf(LIN_MU);
+  double *pt = buf(LIN_PART), *W2 = buf(CON_W2), *H = buf(CON_H), *Lh = buf(CON_LH), *strip = buf(CON_STRIP), *Xt = buf(CON_XT);
+  double *Cq = buf(CON_C), *E = buf(CON_E), *dv = buf(CON_G), *g = dv + Rp, *dchi = dv + 2 * Rp, *bs = buf(CON_BS);
+  double *vsq = buf(CON_VSQ), *vz = buf(CON_VZ), *omu = buf(CON_OUT), *osd = omu + Mp;
+  hipStream_t st = c->stream;
+
+  // pass 1: gpf_predict_linear's pipeline (B, V_A, G, Q, S = A Sigma A^T and A mu stay on the device)
+  int rc = lin_enqueue(c, knobs, c->n_buf, p, ls, xfit, M, w, R);
+  // b and s, then H and d = b - A mu, W2 = U^T V_A (U lower triangular: the depth tiles k < i are zeros)
+  if (!rc && (hipMemcpyAsync(bs, b, (size_t)R * 8, hipMemcpyHostToDevice, st) != hipSuccess ||
+              hipMemcpyAsync(bs + Rp, sv, (size_t)R * 8, hipMemcpyHostToDevice, st) != hipSuccess ||
+              hipMemsetAsync(Xt, 0, (size_t)Rp * Rp * 8, st) != hipSuccess)) {
+    rc = GPF_HIP_ERROR;
+    c->err = "gpf_predict_conditioned: upload of the measurements failed";
+  }
+  if (!rc)
+    rc = launch(c, PC_PREDK, 16.0 * (double)Rp * Rp, [&] {
+      hipLaunchKernelGGL(gpf::k_con_h, dim3((unsigned)Rp), dim3(NTHR), 0, st, R, Rp, S, bs, bs + Rp, amu, H, dv);
+    });
+  if (!rc)
+    rc = lin_product(c, pt, nt * Rt, Rt, false, nt, (double)Np * Np * Rp, nullptr, 1.0, W2, Rp,
+                     [&](dim3 grid, int per, double* part) {
+                       hipLaunchKernelGGL(gpf::k_con_tn, grid, dim3(gpf::Geo<T>::NTH), 0, st, Rt, nt, per, 1, c->d_U, (int)Np, V,
+                                          Rp, part);
+                     });
+  // the training factorisation's status before the dense one starts (as gpf_posterior_draws), then
+  // H = Lh Lh^T without jitter; the ladder waits for its status word, so both are known before the
+  // first chunk: nothing reaches the caller's buffers after a failure
+  if (hipStreamSynchronize(st) != hipSuccess && !rc) {
+    rc = GPF_HIP_ERROR;
+    c->err = "gpf_predict_conditioned: synchronisation failed";
+  }
+  if (!rc && (rc = particle_status(c, 0)) == GPF_NOT_PD)
+    c->err = "gpf_predict_conditioned: the covariance of the training points is not positive definite";
+  const double jit0 = 0.0;
+  double jit = 0.0;
+  int tr = 0;
+  if (!rc && (rc = dense_chol_ladder(c, H, Lh, strip, R, Rp, &jit0, 1, &jit, &tr)) == GPF_NOT_PD)
+    c->err = "gpf_predict_conditioned: H = A Sigma A^T + diag(s^2) is not positive definite (redundant functionals "
+             "with zero error?)";
+  // Xt = Lh^-T and g = Lh^-1 d
+  if (!rc)
+    rc = launch(c, PC_PREDK, 16.0 * T * T * Rt, [&] {
+      hipLaunchKernelGGL(gpf::k_dc_inv_diag, dim3((unsigned)Rt), dim3(NTHR), 0, st, strip, Xt, Rp);
+    });
+  for (int I = 1; I < Rt && !rc; ++I) {
+    rc = launch(c, PC_PRED, (double)T * T * T * I * (I + 1), [&] {  // 2 T^3 per 128-deep step, I - J of them for tile J
+      hipLaunchKernelGGL(gpf::k_dc_inv_sum, dim3((unsigned)I), dim3(gpf::DNTH), 0, st, I, Lh, Xt, Rp);
+    });
+    if (!rc)
+      rc = launch(c, PC_PRED, 2.0 * T * T * T * I, [&] {
+        hipLaunchKernelGGL(gpf::k_dc_inv_fin, dim3((unsigned)I), dim3(gpf::DNTH), 0, st, I, strip, Xt, Rp);
+      });
+  }
+  if (!rc)
+    rc = launch(c, PC_LOSS, 0.0, [&] {
+      hipLaunchKernelGGL(gpf::k_con_g, dim3((unsigned)((Rp + NTHR - 1) / NTHR)), dim3(NTHR), 0, st, Rp, Xt, dv, g);
+    });
+  // pass 2: a chunk of query points per pass
+  const int R4 = (R + 3) / 4 * 4;
+  for (int64_t s = 0; s < M && !rc; s += Cc) {
+    const int64_t m = std::min<int64_t>(Cc, M - s);
+    const int nqt = (int)((m + T - 1) / T);
+    const int Cm = nqt * T;
+    rc = launch(c, PC_PREDK, 8.0 * (double)Np * Cm, [&] {
+      gpf::launch_cross_cov(st, (int)c->N, (int)m, (int)Np, Cm, d, c->d_x, (int)c->N, xf + s, (int)Mp, c->d_ls, blk, Cc);
+    });
+    if (rc) break;
+    const double vflops = 2.0 * T * T * (double)Cm * ((double)nt * (nt + 1) / 2) - (double)T * T * Cm * nt;  // (as gpf_predict)
+    rc = launch(c, PC_PRED, vflops, [&] {
+      hipLaunchKernelGGL(gpf::k_predict_vsq, dim3(nqt, nt), dim3(gpf::Geo<T>::NTH), 0, st, (int)Np, c->d_U, blk, (int)Cc, vsq,
+                         c->d_yb, vz, 0);
+    });
+    if (rc) break;
+    // C = G - K_s^T W2 over the chunk's rows, then E = C Lh^-T
+    const double* G1 = G + (size_t)s * Rp;
+    rc = lin_product(c, pt, nqt * Rt, Rt, false, nt, 2.0 * (double)Np * Cm * Rp, G1, -1.0, Cq, Rp,
+                     [&](dim3 grid, int per, double* part) {
+                       hipLaunchKernelGGL(gpf::k_con_tn, grid, dim3(gpf::Geo<T>::NTH), 0, st, Rt, nt, per, 0, blk, (int)Cc, W2, Rp,
+                                          part);
+                     });
+    if (rc) break;
+    rc = lin_product(c, pt, nqt * Rt, Rt, false, Rt, 2.0 * (double)Cm * Rp * Rp, nullptr, 1.0, E, Rp,
+                     [&](dim3 grid, int per, double* part) {
+                       hipLaunchKernelGGL(gpf::k_lin_nn, grid, dim3(gpf::Geo<T>::NTH), 0, st, Rt, Rt, per, Cq, Rp, Xt, Rp, part);
+                     });
+    if (rc) break;
+    rc = launch(c, PC_LOSS, 0.0, [&] {
+      hipLaunchKernelGGL(gpf::k_con_out, dim3((unsigned)((m + NTHR - 1) / NTHR)), dim3(NTHR), 0, st, nt, (int)m, vz, (int)Cc, vsq,
+                         E, Rp, R4, g, omu + s, osd + s, s == 0 ? dchi : nullptr);
+    });
+  }
+  if (!rc) {
+    const size_t row = (size_t)R * 8, pitch = (size_t)Rp * 8;
+    double hchi = 0.0;
+    if (hipMemcpyAsync(mu_out, omu, (size_t)M * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(sd_out, osd, (size_t)M * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        (fmean && hipMemcpyAsync(fmean, amu, row, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+        (fcov && hipMemcpy2DAsync(fcov, row, S, pitch, row, (size_t)R, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+        (chi2 && hipMemcpyAsync(&hchi, dchi, 8, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+        hipStreamSynchronize(st) != hipSuccess) {
+      rc = GPF_HIP_ERROR;
+      c->err = "gpf_predict_conditioned: copy back failed";
+    }
+    if (!rc && chi2) *chi2 = hchi;
+  }
+  hipStreamSynchronize(st);
+  if (c->prof) harvest(c);
+  double held = 0.0;
+  for (int i = 0; i < CON_NBUF; ++i) held += (double)c->n_cap[i];
+  if (held > keep_bytes(knobs)) free_pcon(c);
   return rc;
 }
 

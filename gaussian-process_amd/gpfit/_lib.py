@@ -38,6 +38,8 @@ SIGNATURES = {
     "gpf_predict": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int64, ctypes.c_int64, _dp, _dp]),
     "gpf_predict_cov": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int64, _dp, _dp]),
     "gpf_predict_linear": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int64, _dp, ctypes.c_int, ctypes.c_int64, _dp, _dp, _dp]),
+    "gpf_predict_conditioned": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int64, _dp, ctypes.c_int, _dp, _dp, ctypes.c_int64,
+                                               _dp, _dp, _dp, _dp, _dp]),
     "gpf_chol_dense": (ctypes.c_int, [_vp, _dp, ctypes.c_int64, _dp, ctypes.c_int, _dp, _dp, _ip]),
     "gpf_posterior_draws": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int64, _dp, ctypes.c_int64, _dp, ctypes.c_int,
                                            _dp, _dp, _dp, _dp, _ip]),
@@ -320,6 +322,47 @@ class Context:
                                          _ptr(prior) if want_prior else None)
         self._check(rc, "gpf_predict_linear")
         return (mean, cov, prior) if want_prior else (mean, cov)
+
+    def predict_conditioned(self, lengths, x_fit, weights, values, noise, chunk=0, want_functionals=False):
+        """The latent posterior at x_fit (d, M) conditioned on R measured linear functionals
+        (gpf_predict_conditioned): values[r] = sum_q weights[r, q] f(x_q) + N(0, noise[r]^2), the
+        errors independent, noise[r] >= 0. Returns (mu' (M,), sd' (M,), info) with info["chi2"] =
+        (b - A mu)^T H^-1 (b - A mu), H = A Sigma A^T + diag(noise^2): the agreement of the
+        measurements with the fit before conditioning (about R is expected). With want_functionals
+        also info["fmean"] (R,) and info["fcov"] (R, R): A mu and A Sigma A^T before conditioning,
+        bitwise predict_linear()'s at the same chunk. ``chunk`` as predict_linear. With R = 0 the
+        plain prediction. LinAlgError if the covariance of the training points or H is not positive
+        definite (redundant functionals with zero noise), ValueError for bad arguments."""
+        ls, xf, w = _f64(lengths).reshape(-1), _f64(x_fit), _f64(weights)
+        b, s = _f64(values).reshape(-1), _f64(noise).reshape(-1)
+        if xf.ndim != 2:
+            raise ValueError("x_fit must be (d, M)")
+        if self.d and (xf.shape[0] != self.d or ls.shape[0] != self.d):
+            raise ValueError(f"x_fit must be ({self.d}, M) and lengths ({self.d},)")
+        m = xf.shape[1]
+        if w.ndim != 2 or w.shape[1] != m:
+            raise ValueError(f"weights must be (R, {m})")
+        r = w.shape[0]
+        if b.shape != (r,) or s.shape != (r,):
+            raise ValueError(f"values and noise must be ({r},)")
+        if r == 0:
+            mu, sd = self.predict(ls, xf) if m else (np.empty(0), np.empty(0))
+            info = {"chi2": 0.0}
+            if want_functionals:
+                info.update(fmean=np.empty(0), fcov=np.empty((0, 0)))
+            return mu, sd, info
+        mu, sd = np.empty(m), np.empty(m)
+        fmean = np.empty(r) if want_functionals else None
+        fcov = np.empty((r, r)) if want_functionals else None
+        chi2 = ctypes.c_double(0.0)
+        rc = self.lib.gpf_predict_conditioned(self._h, _ptr(ls), _ptr(xf), m, _ptr(w), r, _ptr(b), _ptr(s), int(chunk),
+                                              _ptr(mu), _ptr(sd), _ptr(fmean) if want_functionals else None,
+                                              _ptr(fcov) if want_functionals else None, ctypes.byref(chi2))
+        self._check(rc, "gpf_predict_conditioned")
+        info = {"chi2": float(chi2.value)}
+        if want_functionals:
+            info.update(fmean=fmean, fcov=fcov)
+        return mu, sd, info
 
     def chol_dense(self, a, jitters=JITTERS):
         """Cholesky factor of the dense symmetric matrix a (n, n) on the device (gpf_chol_dense):

@@ -138,6 +138,41 @@ int gpf_predict_linear(gpf_ctx* ctx, const double* ls, const double* xfit_dM, in
                        const double* w_RM, int R, int64_t chunk,
                        double* mean_R, double* cov_RR, double* prior_RR);
 
+/* The latent posterior at the M query points xfit_dM (d, M) conditioned on R measured linear
+ * functionals of it: b_R[r] = sum_q w[r,q] f(x_q) + noise_r, noise_r ~ N(0, s_R[r]^2) independent
+ * (an integrated value, averages in another experiment's bins; s_r = 0 is an exact constraint). With
+ * mu, Sigma the posterior of gpf_predict_cov and A = w_RM,
+ *   H = A Sigma A^T + diag(s^2) = Lh Lh^T,  C = Sigma A^T,  E = C Lh^-T,  g = Lh^-1 (b - A mu)
+ *   mu_M[q] = mu_q + E[q,:] . g
+ *   sd_M[q] = sqrt(max((1 - sum v^2) - sum_r E[q,r]^2, 1e-12))      (gpf_predict's variance and clip)
+ *   *chi2   = g . g = (b - A mu)^T H^-1 (b - A mu) (nullable): how well the measurements agree with the
+ *             fit before conditioning; about R is expected.
+ * fmean_R, fcov_RR (nullable): A mu and A Sigma A^T BEFORE conditioning, bitwise gpf_predict_linear's
+ * mean_R and cov_RR for the same inputs and chunk (the same launches in the same order).
+ * Conditioning on one point functional (x_q, b, s) equals adding the training point (x_q, b, s).
+ * chunk as gpf_predict_linear: query points per pass, rounded up to 128, 0 means 16384, capped at
+ * 65536. Nothing of size M x M or Npad x M is allocated: behind gpf_predict_linear's pipeline,
+ * W2 = L^-T V_A (Npad x Rpad) once, H's factor and its inverse (Rpad x Rpad; gpf_chol_dense's kernels,
+ * no jitter, and a blocked forward substitution), then per chunk the K_s block again, gpf_predict's
+ * V = U K_s reduction, C = K_ss A^T - K_s^T W2 and E (chunk x Rpad each). On the device for the call:
+ * what gpf_predict_linear holds, the Npad x Rpad, Rpad x Rpad and chunk x Rpad operands above, the
+ * partials of V (2 nt x chunk) and mu', sd' (2 Mpad). The call has its own buffers, kept under
+ * GPF_PREDICT_KEEP_MB apart from those of the other prediction calls: interleaved calls of those keep
+ * their bits. If the buffers exceed half of the free device memory, chunk is halved until they fit; if
+ * they do not fit at chunk = 128 the call returns GPF_BAD_ARG and gpf_last_error names the largest M
+ * that fits at this R. Repeating a call with the same chunk gives the same bits (every sum runs in a
+ * fixed order that the shapes alone decide; no floating-point atomics).
+ * GPF_NOT_PD: the covariance of the training points fails as in gpf_predict, or H has a pivot <= 0
+ * (redundant functionals with zero error; no jitter is added); gpf_last_error says which. Every
+ * output is then untouched (both factorisations finish before anything is copied back).
+ * GPF_BAD_ARG, before any device work: everything gpf_predict_linear rejects, a null b_R, s_R, mu_M or
+ * sd_M with M > 0 and R > 0, a non-finite b, an s_r that is negative or not finite, R > 1024 (larger R
+ * is not built yet: the inverse of H's factor is formed densely). M == 0 or R == 0 returns GPF_OK and
+ * writes nothing. */
+int gpf_predict_conditioned(gpf_ctx* ctx, const double* ls, const double* xfit_dM, int64_t M,
+                            const double* w_RM, int R, const double* b_R, const double* s_R, int64_t chunk,
+                            double* mu_M, double* sd_M, double* fmean_R, double* fcov_RR, double* chi2);
+
 /* Cholesky factor of a dense symmetric host matrix on the device: tries A + jitters[t] I for
  * t = 0, 1, .. until one factorises. L_nn: n x n row-major, zeros above the diagonal.
  * Only A's lower triangle is read. A blocked left-looking factorisation on 128-tiles with FP64
@@ -299,12 +334,17 @@ int gpf_set_profiling(gpf_ctx* ctx, int on);
  *       (gpf_predict_cov: its V = U K_s and Sigma = K_ss - V^T V kernels, one launch each;
  *       gpf_chol_dense / gpf_posterior_draws: also the dense factorisation's launches and k_draws;
  *       gpf_predict_linear: its skinny products — a k_lin_nn or k_lin_tn launch with the product's
- *       flops 2 rows depth Rpad, and the k_lin_reduce launch behind it with none — and k_predict_v)
+ *       flops 2 rows depth Rpad, and the k_lin_reduce launch behind it with none — and k_predict_v;
+ *       gpf_predict_conditioned: gpf_predict_linear's, its k_con_tn / k_lin_nn products counted the
+ *       same way, the dense factorisation of H, k_dc_inv_sum / k_dc_inv_fin and gpf_predict's
+ *       k_predict_vsq per chunk)
  *  [18] prediction cross-covariance ms  [19] launches  [20] algorithmic bytes
  *       (gpf_predict_cov: K_s and K_ss in one entry, and the mirror copy of Sigma's lower triangle;
  *       gpf_chol_dense: the padding and mirror copy of the uploaded matrix;
  *       gpf_predict_linear: one entry per kernel block built, 8 bytes per element, the transposed
- *       copy of the weights and the two mirror copies)
+ *       copy of the weights and the two mirror copies;
+ *       gpf_predict_conditioned: gpf_predict_linear's, the K_s block of every chunk once more, k_con_h
+ *       and k_dc_inv_diag)
  *  [21] probability-surface kernel ms  [22] launches  [23] algorithmic bytes
  *  [24] shader clock (MHz) the factor kernels held while they ran (every workgroup's span in
  *       s_memtime clocks over its span in the 100 MHz s_memrealtime clock; profiled batches only)
