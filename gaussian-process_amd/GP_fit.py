@@ -8,8 +8,10 @@ messages follow GP_fit.py:20-164.
 Optional options.yaml keys (absent = reference behaviour): pso_num_particles (40),
 pso_max_iter (500), pso_max_points (100), pso_seed (none: unseeded global RNG);
 len_scale_objective ("calibration": the reference's swarm; "marginal_likelihood": the
-maximum-marginal-likelihood fit, which reuses pso_max_points and pso_seed) and
-mle_num_starts (40).
+maximum-marginal-likelihood fit, which reuses pso_max_points and pso_seed),
+mle_num_starts (40) and hyper_samples (K >= 1: the written mean and sd are marginalised over K
+length-scale samples, gpfit.hyper.predict_marginal, instead of taken at the one fitted vector; it
+reuses pso_max_points and pso_seed).
 """
 from functools import reduce
 from pathlib import Path
@@ -38,19 +40,50 @@ def _pso_overrides(options_path="options.yaml"):
     return {kw: opts[key] for key, kw in _PSO_KEYS.items() if opts.get(key) is not None}
 
 
+def _hyper_samples(options_path="options.yaml"):
+    """options.yaml's hyper_samples as an int K >= 1, or None (absent: the reference's prediction at the
+    fitted length scales, byte-identical outputs)."""
+    try:
+        with open(options_path, "r") as f:
+            opts = yaml.safe_load(f) or {}
+    except OSError:
+        return None
+    k = opts.get("hyper_samples")
+    if k is None:
+        return None
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError(f"options.yaml: hyper_samples must be an integer >= 1, not {k!r}")
+    return k
+
+
+def _marginal(x_known, y_known, e_known, x_fit, ls, k, pso):
+    """predict_marginal's mean and sd at K samples around the marginal likelihood's optimum: the fitted
+    vector when the fit maximised it, else gpfit.mle.fit_lml's (the swarm's optimum of the calibration
+    loss is not the centre of the likelihood)."""
+    from gpfit.hyper import predict_marginal
+    kw = {key: pso[key] for key in ("max_points", "seed") if key in pso}
+    best = ls if pso.get("objective") == "marginal_likelihood" else None
+    mu, sd, _ = predict_marginal(x_known, y_known, e_known, x_fit, best_l=best, n_samples=k, **kw)
+    return mu, sd
+
+
 def _merge(frames, on):
     return reduce(lambda a, b: pd.merge(a, b, on=on, how="outer"), frames).fillna(float("inf"))
 
 
 def process_experiment(x_known, y_known, e_known, resolution, dim_labels, filename, exp_idx, total_exps,
-                       PSO_progress, **pso):
-    """Length scales by PSO, hull grid, GP prediction -> DataFrame (GP_fit.py:20-46)."""
+                       PSO_progress, hyper_samples=None, **pso):
+    """Length scales by PSO, hull grid, GP prediction -> DataFrame (GP_fit.py:20-46). hyper_samples=K
+    writes the prediction marginalised over K length-scale samples instead of GP's."""
     if x_known.shape[1] == 0:
         print("  Skipping experiment: no valid data points")
         return None
     ls = len_scale_opt(x_known, y_known, e_known, PSO_progress, **pso)
     grid = fill_convex_hull(x_known.T, resolution)
-    mu, sd = GP(x_known, y_known, e_known, grid.T, ls)
+    if hyper_samples is None:
+        mu, sd = GP(x_known, y_known, e_known, grid.T, ls)
+    else:
+        mu, sd = _marginal(x_known, y_known, e_known, grid.T, ls, hyper_samples, pso)
     frame = pd.DataFrame(grid, columns=dim_labels)
     if total_exps == 1:
         qcol, ecol = f"{filename}", f"{filename}_unc"
@@ -101,6 +134,9 @@ def create_GP():
     """
     resolution, progress, out_name, labels, data_list, write_ind, group_exps = read_yaml()
     pso = _pso_overrides()
+    hyper = _hyper_samples()
+    if hyper is not None:
+        pso = dict(pso, hyper_samples=hyper)
     nd = len(resolution)
     dim_labels = labels[:nd]
     out_path = Path(out_name) if out_name else Path("GP_results.txt")

@@ -70,6 +70,17 @@ def GP_conditioned(x_known, y_known, e_known, x_fit, lengths, weights, values, n
     return predict_conditioned(x_known, y_known, e_known, x_fit, lengths, weights, values, noise, method="stream")[:2]
 
 
+def GP_marginal(x_known, y_known, e_known, x_fit, lengths_Pd, weights=None):
+    """GP()'s (mu, sigma) at x_fit (d, M) with the length scales marginalised over the samples
+    lengths_Pd (P, d) with the weights (P,) (None: equal) instead of fixed: the mixture of the P
+    predictions by the law of total variance, mix_mu = sum_p w_p mu_p and
+    mix_sigma^2 = sum_p w_p (sigma_p^2 + (mu_p - mix_mu)^2), from one batched factorisation on the
+    device (gpf_predict_batch). gpfit.hyper.sample_hyper draws samples and weights from the marginal
+    likelihood."""
+    from gpfit.hyper import predict_marginal
+    return predict_marginal(x_known, y_known, e_known, x_fit, ls=lengths_Pd, weights=weights, method="batch")[:2]
+
+
 def GP_draws(x_known, y_known, e_known, x_fit, lengths, n_draws, seed=None, method="host"):
     """n_draws joint draws of the latent GP at x_fit: (n_draws, M), from N(GP_cov's mu, cov) by a
     Cholesky factor of cov + jitter I: method="host" takes it with NumPy from the copied-back cov

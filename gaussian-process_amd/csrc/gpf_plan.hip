@@ -32,7 +32,7 @@ struct Knob {
 struct Knobs {
   Knob persist, groups, step_group, split_k, split_k_slots, split_k_minch, early_diag, defer_syrk, lookahead, reorder,
       pair, pair_sync, la_all, la_all_pb, la_all_from, la_all_first, wait_spins, step_1percu, la_delay_test,
-      no_graph, mem_fraction, max_chunk, predict_keep_mb;
+      no_graph, mem_fraction, max_chunk, predict_keep_mb, predbatch_order, predbatch_ks;
   static Knobs from_env() {
     auto rd = [](const char* name) {
       Knob k;
@@ -63,6 +63,8 @@ struct Knobs {
     k.mem_fraction = rd("GPF_MEM_FRACTION");
     k.max_chunk = rd("GPF_MAX_CHUNK");
     k.predict_keep_mb = rd("GPF_PREDICT_KEEP_MB");
+    k.predbatch_order = rd("GPF_PREDBATCH_ORDER");
+    k.predbatch_ks = rd("GPF_PREDBATCH_KS");
     return k;
   }
 };

@@ -25,6 +25,7 @@
 #include "gpf_persist.hip"
 #include "gpf_objective.hip"
 #include "gpf_predict.hip"
+#include "gpf_predbatch.hip"
 #include "gpf_postcov.hip"
 #include "gpf_linear.hip"
 #include "gpf_densechol.hip"
@@ -148,6 +149,13 @@ struct gpf_ctx {
   // (CON_*), apart from all of the above and kept under the same rule
   void* n_buf[32] = {};
   size_t n_cap[32] = {};
+  // gpf_predict_batch's buffers, apart from all of the above and kept under the same rule: the query
+  // coordinates (d x Mpad), the chunk's K_s blocks (pc x Npad x Cq), the vsq / vz partials
+  // (pc x nt x Cq each), the weights, the mixture state (4 x Mpad), (mix_mu | mix_sd), the per-particle
+  // staging block (2 x pc x Cq) and its pinned host copy
+  Scratch b_xf, b_ks, b_vsq, b_vz, b_w, b_state, b_mix, b_each;
+  double* b_heach = nullptr;
+  size_t b_heach_cap = 0;
   // gpf_chol_dense's matrix, factor and U_JJ strip (grow-only, kept under the same rule); the status
   // word of a dense factorisation sits behind its strip (dense_chol_strip_bytes)
   Scratch dc_a, dc_l, dc_u;
@@ -306,6 +314,13 @@ static void free_pcon(gpf_ctx* c) {
   }
 }
 
+static void free_pbatch(gpf_ctx* c) {
+  for (Scratch* s : {&c->b_xf, &c->b_ks, &c->b_vsq, &c->b_vz, &c->b_w, &c->b_state, &c->b_mix, &c->b_each}) s->release();
+  hipHostFree(c->b_heach);
+  c->b_heach = nullptr;
+  c->b_heach_cap = 0;
+}
+
 static void free_dchol(gpf_ctx* c) {
   for (Scratch* s : {&c->dc_a, &c->dc_l, &c->dc_u}) s->release();
 }
@@ -315,6 +330,7 @@ static void free_pred(gpf_ctx* c) {
   free_pdraw(c);
   free_plin(c);
   free_pcon(c);
+  free_pbatch(c);
   free_dchol(c);
   hipFree(c->p_xf); hipFree(c->p_ks); hipFree(c->p_vsq); hipFree(c->p_mu); hipFree(c->p_sd); hipFree(c->p_vz);
   hipHostFree(c->p_hx); hipHostFree(c->p_hout);
@@ -2074,6 +2090,264 @@ int gpf_lml_batch(gpf_ctx* c, const double* ls, int P, double* lml, double* grad
     }
   }
   return ret;
+}
+
+// ---- gpf_predict_batch: prediction for a batch of length-scale samples and their mixture ----
+
+// Device bytes of a gpf_predict_batch pass per particle and padded query column (the K_s column, the
+// vsq / vz partials, the staging of mu_p, sd_p and var_p) ...
+static double pbatch_col_bytes(const gpf_ctx* c) { return 8.0 * ((double)c->Npad + 2.0 * c->nt + 3.0); }
+// ... and of the call whatever the chunks: the coordinates, the mixture state, (mix_mu | mix_sd), the weights
+static double pbatch_fixed_bytes(const gpf_ctx* c, int64_t Mp, int P) { return 8.0 * ((c->d + 6.0) * (double)Mp + P); }
+
+static double pbatch_held(const gpf_ctx* c) {
+  double b = 0.0;
+  for (const Scratch* s : {&c->b_xf, &c->b_ks, &c->b_vsq, &c->b_vz, &c->b_w, &c->b_state, &c->b_mix, &c->b_each}) b += (double)s->cap;
+  return b;
+}
+
+// The particle-chunk capacity pc and the query chunk cq (padded columns per pass) of a
+// gpf_predict_batch call, planned together: ensure_work alone sizes the factorisation workspace to
+// GPF_MEM_FRACTION (0.85) of the free memory, which at large N leaves no room for the particles'
+// K_s blocks. The workspace of pc particles is taken first; the call's own buffers (fixed +
+// pc col cq bytes) must then fit half of what is left. A workspace the context already holds with
+// at least pc slots is kept if the buffers fit beside it; if they do not (an earlier batch took
+// most of the memory) it is given back and regrown to pc slots (regrow). The query chunk is halved
+// down to 128 before the particle chunk shrinks (by a quarter per step): a smaller query chunk costs
+// launches, a smaller particle chunk changes the factorisation's schedule. keep > 0 (chunk = 0, the
+// default): the chunk also stays within GPF_PREDICT_KEEP_MB while that leaves at least 512 columns per
+// pass, so that the next call finds the buffers (DESIGN.md 2h has the measurement).
+// Pure: free_b = free device bytes, held_b = this call's kept buffers, cap slots of per bytes held.
+struct PbatchPlan {
+  int pc = 0;
+  int64_t cq = 0;
+  bool regrow = false;
+  double left = 0.0;  // what the last candidate had for the call's buffers (for the error message)
+};
+static bool pbatch_plan_pure(double free_b, double held_b, int cap, double per, double col, double fixed, int pc0, int64_t cq0,
+                             double keep, double frac, PbatchPlan* out) {
+  // what a regrown workspace starts from: free_work returns the old one and this call's kept buffers
+  const double avail = free_b + held_b, avail_regrown = avail + (double)cap * per;
+  int pc = std::max(1, pc0);
+  if (cap < pc) pc = (int)std::max(1.0, std::min((double)pc, std::floor(avail_regrown * frac / per)));
+  for (;;) {
+    for (int regrow = cap >= pc ? 0 : 1; regrow < 2; ++regrow) {
+      if (regrow && (double)pc * per > avail_regrown * frac) continue;  // (ensure_work would give fewer slots)
+      const double left = regrow ? avail_regrown - (double)pc * per : avail;
+      out->left = left;
+      int64_t cq = cq0;
+      while (cq > T && fixed + (double)pc * col * (double)cq > 0.5 * left) cq = ((cq / 2 + T - 1) / T) * T;
+      if (keep > 0.0 && fixed + (double)pc * col * (double)cq > keep) {
+        const int64_t kq = (int64_t)((keep - fixed) / ((double)pc * col)) / T * T;
+        if (kq >= 512) cq = std::min(cq, kq);
+      }
+      if (fixed + (double)pc * col * (double)cq <= 0.5 * left) {
+        out->pc = pc;
+        out->cq = cq;
+        out->regrow = regrow && cap >= pc;  // (cap < pc: ensure_work regrows anyway)
+        return true;
+      }
+    }
+    if (pc == 1) return false;
+    pc -= std::max(1, pc / 4);
+  }
+}
+
+static int pbatch_plan(gpf_ctx* c, const Knobs& k, int P, int64_t M, int64_t chunk, PbatchPlan* plan) {
+  const int64_t Mp = ((M + T - 1) / T) * T;
+  int64_t cq0 = chunk > 0 ? std::min<int64_t>(chunk, 65536) : 16384;
+  cq0 = std::min<int64_t>(((cq0 + T - 1) / T) * T, Mp);
+  size_t fr = 0, tot = 0;
+  GPF_HIP(c, hipMemGetInfo(&fr, &tot));
+  const double per = (double)bytes_per_particle(c), col = pbatch_col_bytes(c), fixed = pbatch_fixed_bytes(c, Mp, P);
+  int pc = std::min(P, 65535);  // (the particle is a grid axis of k_predict_vsq_batch)
+  if (k.max_chunk.set) pc = (int)std::max<long long>(1, std::min<long long>(pc, k.max_chunk.i));
+  if (pbatch_plan_pure((double)fr, pbatch_held(c), c->cap, per, col, fixed, pc, cq0, chunk == 0 ? keep_bytes(k) : 0.0,
+                       k.mem_fraction.set ? k.mem_fraction.f : 0.85, plan))
+    return GPF_OK;
+  const double mfit = (0.5 * plan->left - col * T) / (8.0 * (c->d + 6.0));
+  const double all = (double)fr + pbatch_held(c) + (double)c->cap * per;
+  c->err = "gpf_predict_batch: N=" + std::to_string(c->N) + ", M=" + std::to_string(M) +
+           " do not fit half of the free device memory with one particle at chunk 128: " +
+           (mfit >= 1.0 ? "the largest M that fits at this N is about " + std::to_string((long long)mfit)
+                        : "the largest N that fits is about " +
+                              std::to_string((long long)std::max(0.0, std::sqrt(std::max(0.0, 0.5 * all) / 16.0))));
+  return GPF_BAD_ARG;
+}
+
+int gpf_predict_batch(gpf_ctx* c, const double* ls, int P, const double* w, const double* xfit, int64_t M, int64_t chunk,
+                      double* mix_mu, double* mix_sd, double* mu_PM, double* sd_PM, int* bad_idx) {
+  if (!c) return GPF_BAD_ARG;
+  if (bad_idx) *bad_idx = -1;
+  if (c->N <= 0) return bad_arg(c, "gpf_predict_batch: call gpf_set_data first");
+  if (P < 0 || M < 0 || chunk < 0) return bad_arg(c, "gpf_predict_batch: P, M and chunk must be >= 0");
+  if (M > (int64_t)1 << 30) return bad_arg(c, "gpf_predict_batch: M too large");
+  if (P > 0 && M > 0 && (!ls || !xfit || !mix_mu || !mix_sd)) return bad_arg(c, "gpf_predict_batch: null buffer");
+  const int d = c->d, nt = c->nt;
+  if (ls)
+    for (size_t i = 0; i < (size_t)P * d; ++i)
+      if (!(ls[i] > 0.0) || !std::isfinite(ls[i])) return bad_arg(c, "gpf_predict_batch: length scales must be finite and > 0");
+  // the weights, normalised to sum 1 (null: equal)
+  std::vector<double> wn((size_t)P, P > 0 ? 1.0 / (double)P : 0.0);
+  if (w && P > 0) {
+    double sum = 0.0;
+    for (int p = 0; p < P; ++p) {
+      if (!(w[p] >= 0.0) || !std::isfinite(w[p])) return bad_arg(c, "gpf_predict_batch: weights must be finite and >= 0");
+      sum += w[p];
+    }
+    if (!(sum > 0.0) || !std::isfinite(sum)) return bad_arg(c, "gpf_predict_batch: the weights must have a finite sum > 0");
+    for (int p = 0; p < P; ++p) wn[p] = w[p] / sum;
+  }
+  if (P == 0 || M == 0) return GPF_OK;
+  hipSetDevice(c->device);
+  if (c->K <= 0) c->K = 2;  // as gpf_predict: the histogram is sized minimally
+  const Knobs knobs = Knobs::from_env();
+  const int64_t N = c->N, Np = c->Npad, Mp = ((M + T - 1) / T) * T;
+  const bool each = mu_PM || sd_PM;
+  PbatchPlan plan;
+  int rc = pbatch_plan(c, knobs, P, M, chunk, &plan);
+  if (rc) return rc;
+  int cap = plan.pc;
+  const int64_t Cq = plan.cq;
+  // the factorisation workspace first: a (re)allocation there frees this call's buffers too
+  if (plan.regrow) {  // the workspace an earlier, larger batch left would not leave room: back to cap slots
+    GPF_HIP(c, hipStreamSynchronize(c->stream));
+    free_work(c);
+  }
+  if ((rc = ensure_work(c, cap, knobs))) return rc;
+  cap = std::min(cap, c->cap);
+  const size_t npc = (size_t)cap * (size_t)Cq;
+  if ((rc = c->b_xf.grow(c, (size_t)d * Mp * 8, false, true))) return rc;
+  if ((rc = c->b_ks.grow(c, npc * Np * 8, false, true))) return rc;
+  if ((rc = c->b_vsq.grow(c, npc * nt * 8, false, true))) return rc;
+  if ((rc = c->b_vz.grow(c, npc * nt * 8, false, true))) return rc;
+  if ((rc = c->b_w.grow(c, (size_t)P * 8, false, true))) return rc;
+  if ((rc = c->b_state.grow(c, (size_t)4 * Mp * 8, false, true))) return rc;
+  if ((rc = c->b_mix.grow(c, (size_t)2 * Mp * 8, false, true))) return rc;
+  if ((rc = c->b_each.grow(c, 3 * npc * 8, false, true))) return rc;  // (mu_p | sd_p | var_p), pc x Cq each
+  if (each) {
+    if (c->b_heach_cap < 2 * npc * 8) {
+      hipHostFree(c->b_heach);
+      c->b_heach = nullptr;
+      c->b_heach_cap = 0;
+      GPF_HIP(c, hipHostMalloc((void**)&c->b_heach, 2 * npc * 8, hipHostMallocDefault));
+      c->b_heach_cap = 2 * npc * 8;
+    }
+  }
+  double *d_xf = c->b_xf.as<double>(), *d_ks = c->b_ks.as<double>(), *d_vsq = c->b_vsq.as<double>();
+  double *d_vz = c->b_vz.as<double>(), *d_w = c->b_w.as<double>(), *d_st = c->b_state.as<double>();
+  double *d_mix = c->b_mix.as<double>(), *d_emu = c->b_each.as<double>(), *d_evar = d_emu + 2 * npc;
+  double* d_esd = each ? d_emu + npc : nullptr;
+  // the query coordinates (leading dimension Mp), the weights and the zeroed mixture state, once
+  GPF_HIP(c, hipMemcpy2DAsync(d_xf, (size_t)Mp * 8, xfit, (size_t)M * 8, (size_t)M * 8, (size_t)d, hipMemcpyHostToDevice,
+                              c->stream));
+  GPF_HIP(c, hipMemcpyAsync(d_w, wn.data(), (size_t)P * 8, hipMemcpyHostToDevice, c->stream));
+  GPF_HIP(c, hipMemsetAsync(d_st, 0, (size_t)4 * Mp * 8, c->stream));
+  // 0: one particle after the other; 1: the deepest row tiles of all particles first (k_predict_vsq_batch)
+  // (default by pass: where one particle's tiles of a full pass fill the 512 resident workgroup slots its
+  // operands are shared while it runs, order 0; where they do not, several particles are resident either way
+  // and the shorter tail wins, order 1 — at N=4096, P=64: 0.97-0.98x the time at 79 column tiles, 1.05-1.08x
+  // at 7)
+  const int nqt_full = (int)(std::min<int64_t>(Cq, Mp) / T);
+  const int order = knobs.predbatch_order.num((long long)nqt_full * nt < 512 ? 1 : 0) != 0;
+  // the K_s blocks: 1: k_cross_cov_batch, one launch per pass; 0: k_cross_cov once per particle (bitwise equal)
+  const bool ks_batched = knobs.predbatch_ks.flag(true);
+  for (int s = 0; s < P && rc == GPF_OK; s += cap) {
+    const int pc = std::min(cap, P - s);
+    std::memcpy(c->h_ls, ls + (size_t)s * d, (size_t)pc * d * 8);
+    GPF_HIP(c, hipMemcpyAsync(c->d_ls, c->h_ls, (size_t)pc * d * 8, hipMemcpyHostToDevice, c->stream));
+    GPF_HIP(c, hipMemsetAsync(c->d_info, 0, (size_t)pc * 4, c->stream));
+    if ((rc = run_factor(c, pc, knobs))) break;
+    GPF_HIP(c, hipMemcpyAsync(c->h_info, c->d_info, (size_t)pc * 4, hipMemcpyDeviceToHost, c->stream));
+    for (int64_t s0 = 0; s0 < M && rc == GPF_OK; s0 += Cq) {
+      const int64_t m = std::min<int64_t>(Cq, M - s0);
+      const int nqt = (int)((m + T - 1) / T);
+      const int Cm = nqt * T;
+      // the particles' K_s blocks (Np x Cm, leading dimension Cq), every element bitwise gpf_predict's: one
+      // k_cross_cov_batch launch (at N=100, P=64 the 64 launches of k_cross_cov took 0.51 of the call's 1.2 ms,
+      // the one launch 0.13; profiles/predict_batch/bench.json)
+      rc = launch(c, PC_PREDK, 8.0 * Np * Cm * (double)pc, [&] {
+        if (ks_batched) {
+          gpf::launch_cross_cov_batch(c->stream, pc, (int)N, (int)m, (int)Np, Cm, d, c->d_x, (int)N, d_xf + s0, (int)Mp,
+                                      c->d_ls, d_ks, Cq, (size_t)Np * Cq);
+          return;
+        }
+        for (int q = 0; q < pc; ++q)
+          gpf::launch_cross_cov(c->stream, (int)N, (int)m, (int)Np, Cm, d, c->d_x, (int)N, d_xf + s0, (int)Mp,
+                                c->d_ls + (size_t)q * d, d_ks + (size_t)q * Np * Cq, Cq);
+      });
+      if (rc) break;
+      const double vflops = 2.0 * T * T * (double)Cm * ((double)nt * (nt + 1) / 2) - (double)T * T * Cm * nt;
+      rc = launch(c, PC_PRED, vflops * pc, [&] {
+        hipLaunchKernelGGL(gpf::k_predict_vsq_batch, order ? dim3(nqt, pc, nt) : dim3(nqt, nt, pc), dim3(gpf::Geo<T>::NTH), 0,
+                           c->stream, (int)Np, nt, c->d_U, d_ks, (int)Cq, (size_t)Np * Cq, d_vsq, c->d_yb, d_vz, order);
+      });
+      if (rc) break;
+      rc = launch(c, PC_LOSS, 0.0, [&] {
+        hipLaunchKernelGGL(gpf::k_predict_each, dim3((unsigned)((m + NTHR - 1) / NTHR), pc), dim3(NTHR), 0, c->stream, nt,
+                           (int)m, d_vz, d_vsq, (int)Cq, d_emu, d_evar, d_esd, Cq);
+        hipLaunchKernelGGL(gpf::k_predict_mix, dim3((unsigned)((m + NTHR - 1) / NTHR)), dim3(NTHR), 0, c->stream, (int)m, pc,
+                           d_emu, d_evar, Cq, d_w + s, d_st + s0, Mp);
+      });
+      if (rc) break;
+      if (each) {
+        if (hipMemcpyAsync(c->b_heach, d_emu, 2 * npc * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+            hipStreamSynchronize(c->stream) != hipSuccess) {
+          rc = GPF_HIP_ERROR;
+          c->err = "gpf_predict_batch: copy back failed";
+          break;
+        }
+        for (int q = 0; q < pc; ++q) {
+          if (mu_PM) std::memcpy(mu_PM + (size_t)(s + q) * M + s0, c->b_heach + (size_t)q * Cq, (size_t)m * 8);
+          if (sd_PM) std::memcpy(sd_PM + (size_t)(s + q) * M + s0, c->b_heach + npc + (size_t)q * Cq, (size_t)m * 8);
+        }
+      }
+    }
+    if (rc) break;
+    if (hipStreamSynchronize(c->stream) != hipSuccess) {
+      rc = GPF_HIP_ERROR;
+      c->err = "gpf_predict_batch: synchronisation failed";
+      break;
+    }
+    if (c->prof) harvest(c);
+    for (int q = 0; q < pc && rc == GPF_OK; ++q) {
+      rc = particle_status(c, q);
+      if (rc == GPF_NOT_PD && bad_idx) *bad_idx = s + q;
+    }
+  }
+  if (rc == GPF_OK) {
+    rc = launch(c, PC_LOSS, 0.0, [&] {
+      hipLaunchKernelGGL(gpf::k_predict_mix_out, dim3((unsigned)((M + NTHR - 1) / NTHR)), dim3(NTHR), 0, c->stream, M, d_st, Mp,
+                         d_mix, d_mix + Mp);
+    });
+    if (rc == GPF_OK && (hipMemcpyAsync(mix_mu, d_mix, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+                         hipMemcpyAsync(mix_sd, d_mix + Mp, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess)) {
+      rc = GPF_HIP_ERROR;
+      c->err = "gpf_predict_batch: copy back failed";
+    }
+  }
+  hipStreamSynchronize(c->stream);
+  if (c->prof) harvest(c);
+  if (pbatch_held(c) > keep_bytes(knobs)) free_pbatch(c);
+  return rc;
+}
+
+// Host-only: gpf_predict_batch's memory plan for given byte counts (no device, no context): see gpfit.h.
+int gpf_predict_batch_plan(double free_b, double held_b, int cap_slots, double per_particle_b, double per_col_b, double fixed_b,
+                           int P, int64_t Mpad, int64_t chunk, double keep_b, double mem_fraction, int* pc, int64_t* cq,
+                           int* regrow) {
+  if (!pc || !cq || !regrow || P < 1 || Mpad < T || Mpad % T || chunk < 0 || !(per_particle_b > 0.0) || !(per_col_b > 0.0))
+    return GPF_BAD_ARG;
+  int64_t cq0 = chunk > 0 ? std::min<int64_t>(chunk, 65536) : 16384;
+  cq0 = std::min<int64_t>(((cq0 + T - 1) / T) * T, Mpad);
+  PbatchPlan plan;
+  if (!pbatch_plan_pure(free_b, held_b, cap_slots, per_particle_b, per_col_b, fixed_b, std::min(P, 65535), cq0,
+                        chunk == 0 ? keep_b : 0.0, mem_fraction, &plan))
+    return GPF_BAD_ARG;
+  *pc = plan.pc;
+  *cq = plan.cq;
+  *regrow = plan.regrow ? 1 : 0;
+  return GPF_OK;
 }
 
 // Host-only structural check of the k_step dispatch plan (no device, no context): see gpfit.h.

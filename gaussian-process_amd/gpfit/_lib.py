@@ -46,6 +46,11 @@ SIGNATURES = {
     "gpf_kernel": (ctypes.c_int, [_vp, _dp, ctypes.c_int64, _dp, ctypes.c_int64, ctypes.c_int, _dp, _dp]),
     "gpf_log_marginal_likelihood": (ctypes.c_int, [_vp, _dp, _dp]),
     "gpf_lml_batch": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _dp, _dp, _ip, _ip]),
+    "gpf_predict_batch": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _dp, _dp, ctypes.c_int64, ctypes.c_int64,
+                                         _dp, _dp, _dp, _dp, _ip]),
+    "gpf_predict_batch_plan": (ctypes.c_int, [ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                              ctypes.c_double, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_double,
+                                              ctypes.c_double, _ip, ctypes.POINTER(ctypes.c_int64), _ip]),
     "gpf_set_profiling": (ctypes.c_int, [_vp, ctypes.c_int]),
     "gpf_get_profile": (ctypes.c_int, [_vp, _dp, ctypes.c_int]),
     "gpf_reset_profile": (ctypes.c_int, [_vp]),
@@ -121,6 +126,20 @@ def plan_check(particles, nt):
     keys = ("launches", "workgroups", "whole_tiles", "split_tiles", "S", "Smax", "groups", "diag_workgroups",
             "syrk_workgroups", "persistent", "lead_launches")
     return dict(zip(keys, list(stats)))
+
+
+def predict_batch_plan(free_b, held_b, cap_slots, per_particle_b, per_col_b, fixed_b, particles, m_pad, chunk=0,
+                       keep_b=2048 * 1048576.0, mem_fraction=0.85):
+    """gpf_predict_batch's memory plan for given byte counts (gpf_predict_batch_plan; host only):
+    {"pc", "cq", "regrow"}, or ValueError if one particle at chunk 128 does not fit."""
+    lib = load_library()
+    pc, cq, regrow = ctypes.c_int(0), ctypes.c_int64(0), ctypes.c_int(0)
+    rc = lib.gpf_predict_batch_plan(float(free_b), float(held_b), int(cap_slots), float(per_particle_b), float(per_col_b),
+                                    float(fixed_b), int(particles), int(m_pad), int(chunk), float(keep_b), float(mem_fraction),
+                                    ctypes.byref(pc), ctypes.byref(cq), ctypes.byref(regrow))
+    if rc != GPF_OK:
+        raise ValueError("predict_batch_plan: does not fit, or bad arguments")
+    return {"pc": pc.value, "cq": cq.value, "regrow": bool(regrow.value)}
 
 
 def _f64(a):
@@ -456,6 +475,44 @@ class Context:
         if rc != GPF_NOT_PD or strict:
             self._check(rc, "gpf_lml_batch", bad)
         return lml, g
+
+    def predict_batch(self, positions, x_fit, weights=None, chunk=0, want_each=False):
+        """predict() at every row of positions (P, d) in one batched call, and the mixture of the P
+        predictions with the weights (P,) (None: equal; normalised to sum 1) by the law of total
+        variance (gpf_predict_batch): (mix_mu (M,), mix_sd (M,), info). With want_each, info["mu"] and
+        info["sd"] are the particles' own (P, M) predictions. ``chunk``: query points per pass (rounded
+        up to 128; 0: the library's default); it does not change the bits. P = 1 is bitwise predict().
+        LinAlgError with .particle set to the first row whose covariance is not positive definite,
+        ValueError for bad arguments, P = 0 among them (the C call writes nothing then)."""
+        P, xf = _f64(positions), _f64(x_fit)
+        if P.ndim == 1:
+            P = P.reshape(1, -1)
+        if P.ndim != 2 or xf.ndim != 2:
+            raise ValueError("positions must be (P, d) and x_fit (d, M)")
+        if P.shape[1] != xf.shape[0] or (self.d and xf.shape[0] != self.d):
+            raise ValueError(f"positions must be (P, {self.d or xf.shape[0]}) and x_fit ({self.d or xf.shape[0]}, M)")
+        n, m = P.shape[0], xf.shape[1]
+        if n == 0:
+            raise ValueError("positions is empty: a mixture needs at least one particle")
+        w = None
+        if weights is not None:
+            w = _f64(weights).reshape(-1)
+            if w.shape != (n,):
+                raise ValueError(f"weights must be ({n},)")
+        if int(chunk) < 0:
+            raise ValueError("chunk must be >= 0")
+        mix_mu, mix_sd = np.empty(m), np.empty(m)
+        mu = np.empty((n, m)) if want_each else None
+        sd = np.empty((n, m)) if want_each else None
+        bad = ctypes.c_int(-1)
+        rc = self.lib.gpf_predict_batch(self._h, _ptr(P), n, _ptr(w) if w is not None else None, _ptr(xf), m, int(chunk),
+                                        _ptr(mix_mu), _ptr(mix_sd), _ptr(mu) if want_each else None,
+                                        _ptr(sd) if want_each else None, ctypes.byref(bad))
+        self._check(rc, "gpf_predict_batch", bad)
+        info = {"particles": n}
+        if want_each:
+            info.update(mu=mu, sd=sd)
+        return mix_mu, mix_sd, info
 
     # -- measurement hooks --
     def set_profiling(self, on=True):

@@ -232,6 +232,60 @@ int gpf_log_marginal_likelihood(gpf_ctx* ctx, const double* ls, double* out);
 int gpf_lml_batch(gpf_ctx* ctx, const double* ls_Pd, int P, double* lml_P, double* grad_Pd,
                   int* status_P, int* bad_idx);
 
+/* gpf_predict for P length-scale samples at once, and their mixture: the length scales are not known
+ * exactly (the fit ends with many nearly-as-good candidates), so the prediction is taken at P samples
+ * ls_Pd (P, d) row-major with the weights w_P (nullable: equal; else >= 0, normalised to sum 1 here)
+ * and combined by the law of total variance. Particle p gives mu_p, sd_p exactly as gpf_predict defines
+ * them (latent, amplitude 1, variance clipped at 1e-12), and
+ *   mix_mu_M[q] = sum_p w_p mu_p[q]
+ *   mix_sd_M[q] = sqrt(sum_p w_p (sd_p[q]^2 + (mu_p[q] - mix_mu[q])^2))
+ * mu_PM / sd_PM (nullable, (P, M) row-major) receive every particle's own mu_p / sd_p.
+ * The particles are factorised in chunks by the batched factorisation (as gpf_lml_batch), which leaves
+ * U = L^-1 and z = U y of the whole chunk on the device; per particle chunk and per chunk of query
+ * points the call builds the particles' K_s blocks, reduces V = U K_s of all of them in one launch
+ * (k_predict_vsq_batch: gpf_predict's tile with the particle on a grid axis) and folds the particles'
+ * (mu_p, sd_p) into a per-column mixture state on the device (West's weighted update, the particles in
+ * input order; a particle with weight 0 is predicted but not folded in). The query coordinates are
+ * uploaded once. `chunk`: query points per pass, rounded up to 128; 0 means 16384, lowered to what keeps
+ * the call's buffers within GPF_PREDICT_KEEP_MB (so that the next call finds them) while that leaves at
+ * least 512 columns per pass; capped at 65536. The
+ * particle-chunk capacity and the query chunk are planned together: the factorisation workspace of the
+ * chunk's particles first (GPF_MAX_CHUNK caps it; a larger workspace the context already holds is kept if
+ * the buffers fit beside it, else given back and regrown to the chunk), then the call's own buffers — per pass
+ * pc (Npad + 2 nt + 3) chunk doubles, per call (d + 6) Mpad + P — must fit half of the remaining free
+ * device memory; the query chunk is halved down to 128, then the particle chunk shrinks. If one particle
+ * at chunk 128 does not fit the call returns GPF_BAD_ARG and gpf_last_error names the largest M (or N)
+ * that fits. The call has buffers of its own, kept under GPF_PREDICT_KEEP_MB apart from those of every
+ * other prediction call: interleaved calls of those keep their bits.
+ * Repeating a call on the same context and data gives the same bits (fixed-order sums, no
+ * floating-point atomics). Different chunk values give the same bits: every query column's sums are
+ * independent of the other columns. Different particle-chunk capacities (GPF_MAX_CHUNK, free memory)
+ * agree to rounding only, as the factorisation's schedule depends on the batch (gpf_lml_batch).
+ * With P = 1, mu_PM, sd_PM, mix_mu_M and mix_sd_M are bitwise gpf_predict's mu and sd: the same
+ * factorisation plan and every sum in the same order.
+ * GPF_NOT_PD if any particle's covariance fails: *bad_idx is the first such particle in input order,
+ * mix_mu_M and mix_sd_M are untouched and the rows of mu_PM / sd_PM are unspecified (some may have been
+ * written). GPF_BAD_ARG, before any device work: null ctx, no data set, P < 0, M < 0 or chunk < 0,
+ * a null ls_Pd, xfit_dM, mix_mu_M or mix_sd_M with P > 0 and M > 0, a length scale that is not finite and
+ * > 0, a weight that is negative or not finite, weights that sum to 0, M > 2^30. P == 0 or M == 0
+ * returns GPF_OK and writes nothing. */
+int gpf_predict_batch(gpf_ctx* ctx, const double* ls_Pd, int P, const double* w_P,
+                      const double* xfit_dM, int64_t M, int64_t chunk,
+                      double* mix_mu_M, double* mix_sd_M,
+                      double* mu_PM, double* sd_PM, int* bad_idx);
+
+/* Host-only: the memory plan gpf_predict_batch makes (needs no device and no context; the same function,
+ * not a second derivation), for given byte counts: free_b free device bytes, held_b the call's own kept
+ * buffers, cap_slots particle slots of per_particle_b bytes the context's workspace holds, per_col_b bytes
+ * per particle and padded query column of a pass, fixed_b bytes per call, Mpad the padded M, chunk as the
+ * call's, keep_b the GPF_PREDICT_KEEP_MB limit in bytes, mem_fraction GPF_MEM_FRACTION. Writes the
+ * particle-chunk capacity *pc, the query chunk *cq and *regrow = 1 where a workspace of at least *pc slots
+ * is held but has to be given back and regrown to *pc slots for the call's buffers to fit half of what is
+ * left. GPF_BAD_ARG if one particle at chunk 128 does not fit either way, or for a bad argument. */
+int gpf_predict_batch_plan(double free_b, double held_b, int cap_slots, double per_particle_b,
+                           double per_col_b, double fixed_b, int P, int64_t Mpad, int64_t chunk,
+                           double keep_b, double mem_fraction, int* pc, int64_t* cq, int* regrow);
+
 /* Probability surface of merged GP results (replaces calc_prob_surf.py:15-30,67-81; SURVEY.md
  * §8f row 4). tails: M rows x E entries (row-major) = each merged-frame row after its kinematic
  * columns, non-finite = missing. Per row: y[100] (the numpy.linspace grid), p[100] (bin
@@ -337,14 +391,18 @@ int gpf_set_profiling(gpf_ctx* ctx, int on);
  *       flops 2 rows depth Rpad, and the k_lin_reduce launch behind it with none — and k_predict_v;
  *       gpf_predict_conditioned: gpf_predict_linear's, its k_con_tn / k_lin_nn products counted the
  *       same way, the dense factorisation of H, k_dc_inv_sum / k_dc_inv_fin and gpf_predict's
- *       k_predict_vsq per chunk)
+ *       k_predict_vsq per chunk;
+ *       gpf_predict_batch: one k_predict_vsq_batch launch per particle chunk and query chunk, with the
+ *       flops of all its particles)
  *  [18] prediction cross-covariance ms  [19] launches  [20] algorithmic bytes
  *       (gpf_predict_cov: K_s and K_ss in one entry, and the mirror copy of Sigma's lower triangle;
  *       gpf_chol_dense: the padding and mirror copy of the uploaded matrix;
  *       gpf_predict_linear: one entry per kernel block built, 8 bytes per element, the transposed
  *       copy of the weights and the two mirror copies;
  *       gpf_predict_conditioned: gpf_predict_linear's, the K_s block of every chunk once more, k_con_h
- *       and k_dc_inv_diag)
+ *       and k_dc_inv_diag;
+ *       gpf_predict_batch: one entry per particle chunk and query chunk, the K_s blocks of all its
+ *       particles)
  *  [21] probability-surface kernel ms  [22] launches  [23] algorithmic bytes
  *  [24] shader clock (MHz) the factor kernels held while they ran (every workgroup's span in
  *       s_memtime clocks over its span in the 100 MHz s_memrealtime clock; profiled batches only)
