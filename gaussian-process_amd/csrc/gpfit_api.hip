@@ -70,6 +70,66 @@ struct Scratch {
   template <typename V> V* as() const { return static_cast<V*>(p); }
 };
 
+// A kept set is given back after its call when it holds more device memory than GPF_PREDICT_KEEP_MB
+// (default 2048): a one-off large call must not hold HBM that would starve the next factorisation's
+// or hull's allocations
+double keep_bytes(const Knobs& k) { return (k.predict_keep_mb.set ? k.predict_keep_mb.f : 2048.0) * 1048576.0; }
+
+// The buffers one entry point keeps between its calls (gpf_ctx::kept): device buffers and pinned host
+// staging, each with its capacity. A call plans the bytes of every buffer (its *_plan function), uses
+// the set as it is when every buffer fits and otherwise gives the whole set back and allocates it at
+// exactly the planned sizes. No captured graph holds a pointer into a set, so a regrow leaves the
+// graphs alone (unlike Scratch::grow).
+struct KeptSet {
+  static constexpr int NMAX = 32;
+  void* p[NMAX] = {};
+  size_t cap[NMAX] = {};
+  bool pinned[NMAX] = {};
+  bool fits(const size_t* bytes, int n) const {
+    for (int i = 0; i < n; ++i)
+      if (bytes[i] > cap[i]) return false;
+    return true;
+  }
+  // Waits for c->stream (the set's last user may still run), releases the set and allocates buffer i
+  // at bytes[i] (0: none), as pinned host memory where bit i of pinned_mask is set. After a HIP error
+  // the buffers allocated so far stay recorded for the next release().
+  int regrow(gpf_ctx* c, const size_t* bytes, unsigned pinned_mask, int n);
+  double held() const {  // device bytes (the pinned staging is not counted)
+    double b = 0.0;
+    for (int i = 0; i < NMAX; ++i)
+      if (!pinned[i]) b += (double)cap[i];
+    return b;
+  }
+  void release() {
+    for (int i = 0; i < NMAX; ++i) {
+      if (p[i]) pinned[i] ? hipHostFree(p[i]) : hipFree(p[i]);
+      p[i] = nullptr;
+      cap[i] = 0;
+      pinned[i] = false;
+    }
+  }
+  void trim(const Knobs& k) { if (held() > keep_bytes(k)) release(); }
+  template <typename V = double> V* as(int i) const { return static_cast<V*>(p[i]); }
+};
+
+// What an entry point's *_plan function lays out from the call's sizes: the bytes of every buffer of
+// its set and, where the call checks a budget, their device total (LinPlan and ConPlan carry more)
+struct SetPlan {
+  size_t bytes[KeptSet::NMAX];
+  double total;
+};
+
+// The device bytes of a planned set: what counts against the memory budget and the keep rule
+double device_bytes(const size_t* bytes, unsigned pinned_mask, int n) {
+  double b = 0.0;
+  for (int i = 0; i < n; ++i)
+    if (!(pinned_mask >> i & 1)) b += (double)bytes[i];
+  return b;
+}
+
+// The entry points that keep a set
+enum KeptId { KEPT_PRED = 0, KEPT_PCOV, KEPT_PDRAW, KEPT_LIN, KEPT_CON, KEPT_PBATCH, KEPT_DCHOL, KEPT_PSURF, KEPT_N };
+
 }  // namespace
 
 struct gpf_ctx {
@@ -119,52 +179,10 @@ struct gpf_ctx {
   int* d_cflag = nullptr;  // per particle: last diagonal block reduced by a SYRK workgroup (defer_syrk); reset by k_build_cov
   int* d_pst = nullptr;    // the persistent factorisation's counters (gpf::PState: 3 x cap x nt, heads, abort); reset by k_build_cov
   int ncu = 0;             // compute units of the device (the persistent launch's grid: two workgroups per CU)
-  // gpf_predict's query-chunk buffers, kept between calls (grow-only; freed with the work buffers)
-  double *p_xf = nullptr, *p_ks = nullptr, *p_vsq = nullptr, *p_mu = nullptr, *p_sd = nullptr;
-  double *p_hx = nullptr, *p_hout = nullptr;  // pinned staging: query coordinates, (mu, sd)
-  double* p_vz = nullptr;                      // per row tile of V = U K_s: V^T z partials of mu (gpf::k_predict_vsq)
-  int64_t p_cols = 0, p_np = 0;
-  int p_d = 0, p_nt = 0;
-  // gpf_predict_cov's buffers, apart from gpf_predict's (either call leaves the other's alone) and
-  // kept between calls under the same rule: the query coordinates, K_s and V (c_np x c_cols each),
-  // Sigma (c_cols x c_cols), the vsq / vz partials, (mu | sd), and pinned staging for the
-  // coordinates and the mean
-  double *c_xf = nullptr, *c_ks = nullptr, *c_v = nullptr, *c_cov = nullptr, *c_vsq = nullptr, *c_vz = nullptr;
-  double *c_mu = nullptr, *c_hx = nullptr, *c_hmu = nullptr;
-  int64_t c_cols = 0, c_np = 0;
-  int c_d = 0, c_nt = 0;
-  // gpf_posterior_draws' buffers, apart from both of the above and kept under the same rule: a set like
-  // gpf_predict_cov's (g_cols columns), the factor L (g_cols x g_cols), the normals and the draws
-  // (g_rows x g_cols each) and the U_JJ strip (128 x g_cols + gpf::DC_JUNK) of the dense factorisation
-  double *g_xf = nullptr, *g_ks = nullptr, *g_v = nullptr, *g_cov = nullptr, *g_vsq = nullptr, *g_vz = nullptr;
-  double *g_mu = nullptr, *g_hx = nullptr, *g_hmu = nullptr;
-  double *g_L = nullptr, *g_z = nullptr, *g_dr = nullptr, *g_u = nullptr;
-  int64_t g_cols = 0, g_rows = 0, g_np = 0;
-  int g_d = 0, g_nt = 0;
-  // gpf_predict_linear's buffers (LIN_* below), apart from all of the above and kept under the same
-  // rule: each at least l_cap[i] bytes
-  void* l_buf[16] = {};
-  size_t l_cap[16] = {};
-  // gpf_predict_conditioned's buffers: a set like gpf_predict_linear's (LIN_*) and its own behind it
-  // (CON_*), apart from all of the above and kept under the same rule
-  void* n_buf[32] = {};
-  size_t n_cap[32] = {};
-  // gpf_predict_batch's buffers, apart from all of the above and kept under the same rule: the query
-  // coordinates (d x Mpad), the chunk's K_s blocks (pc x Npad x Cq), the vsq / vz partials
-  // (pc x nt x Cq each), the weights, the mixture state (4 x Mpad), (mix_mu | mix_sd), the per-particle
-  // staging block (2 x pc x Cq) and its pinned host copy
-  Scratch b_xf, b_ks, b_vsq, b_vz, b_w, b_state, b_mix, b_each;
-  double* b_heach = nullptr;
-  size_t b_heach_cap = 0;
-  // gpf_chol_dense's matrix, factor and U_JJ strip (grow-only, kept under the same rule); the status
-  // word of a dense factorisation sits behind its strip (dense_chol_strip_bytes)
-  Scratch dc_a, dc_l, dc_u;
-  // gpf_prob_surface's row-chunk buffers, kept between calls like the prediction's
-  double *s_t = nullptr, *s_cmp = nullptr, *s_y = nullptr, *s_p = nullptr;
-  double4* s_info = nullptr;
-  int* s_ok = nullptr;
-  int64_t s_rows = 0;
-  int s_e = 0;
+  // the buffers the posterior entry points and gpf_prob_surface keep between calls, one set each
+  // (PRED_*, PCOV_*, PDRAW_*, LIN_*, CON_*, PBATCH_*, DCHOL_*, PSURF_* below name a set's buffers):
+  // a call touches its own set only; a regrow of the workspace (free_work) releases them all
+  KeptSet kept[KEPT_N];
   int* d_hist = nullptr;
   // gpf_lml_batch: per-tile gradient partials [particles][tiles][d] and the gradient rows behind them,
   // grow-only and outside the chunk workspace (bytes_per_particle): the evaluation path's chunk
@@ -277,87 +295,21 @@ int Scratch::grow(gpf_ctx* c, size_t bytes, bool zero, bool sync) {
   return GPF_OK;
 }
 
-static void free_pcov(gpf_ctx* c) {
-  hipFree(c->c_xf); hipFree(c->c_ks); hipFree(c->c_v); hipFree(c->c_cov); hipFree(c->c_vsq); hipFree(c->c_vz);
-  hipFree(c->c_mu);
-  hipHostFree(c->c_hx); hipHostFree(c->c_hmu);
-  c->c_xf = c->c_ks = c->c_v = c->c_cov = c->c_vsq = c->c_vz = c->c_mu = nullptr;
-  c->c_hx = c->c_hmu = nullptr;
-  c->c_cols = c->c_np = 0;
-  c->c_d = c->c_nt = 0;
-}
-
-static void free_pdraw(gpf_ctx* c) {
-  hipFree(c->g_xf); hipFree(c->g_ks); hipFree(c->g_v); hipFree(c->g_cov); hipFree(c->g_vsq); hipFree(c->g_vz);
-  hipFree(c->g_mu); hipFree(c->g_L); hipFree(c->g_z); hipFree(c->g_dr); hipFree(c->g_u);
-  hipHostFree(c->g_hx); hipHostFree(c->g_hmu);
-  c->g_xf = c->g_ks = c->g_v = c->g_cov = c->g_vsq = c->g_vz = c->g_mu = nullptr;
-  c->g_L = c->g_z = c->g_dr = c->g_u = nullptr;
-  c->g_hx = c->g_hmu = nullptr;
-  c->g_cols = c->g_rows = c->g_np = 0;
-  c->g_d = c->g_nt = 0;
-}
-
-static void free_plin(gpf_ctx* c) {
-  for (int i = 0; i < 16; ++i) {
-    hipFree(c->l_buf[i]);
-    c->l_buf[i] = nullptr;
-    c->l_cap[i] = 0;
+int KeptSet::regrow(gpf_ctx* c, const size_t* bytes, unsigned pinned_mask, int n) {
+  GPF_HIP(c, hipStreamSynchronize(c->stream));
+  release();
+  for (int i = 0; i < n; ++i) {
+    if (!bytes[i]) continue;
+    GPF_HIP(c, (pinned_mask >> i & 1) ? hipHostMalloc(&p[i], bytes[i], hipHostMallocDefault) : hipMalloc(&p[i], bytes[i]));
+    cap[i] = bytes[i];
+    pinned[i] = pinned_mask >> i & 1;
   }
+  return GPF_OK;
 }
-
-static void free_pcon(gpf_ctx* c) {
-  for (int i = 0; i < 32; ++i) {
-    hipFree(c->n_buf[i]);
-    c->n_buf[i] = nullptr;
-    c->n_cap[i] = 0;
-  }
-}
-
-static void free_pbatch(gpf_ctx* c) {
-  for (Scratch* s : {&c->b_xf, &c->b_ks, &c->b_vsq, &c->b_vz, &c->b_w, &c->b_state, &c->b_mix, &c->b_each}) s->release();
-  hipHostFree(c->b_heach);
-  c->b_heach = nullptr;
-  c->b_heach_cap = 0;
-}
-
-static void free_dchol(gpf_ctx* c) {
-  for (Scratch* s : {&c->dc_a, &c->dc_l, &c->dc_u}) s->release();
-}
-
-static void free_pred(gpf_ctx* c) {
-  free_pcov(c);
-  free_pdraw(c);
-  free_plin(c);
-  free_pcon(c);
-  free_pbatch(c);
-  free_dchol(c);
-  hipFree(c->p_xf); hipFree(c->p_ks); hipFree(c->p_vsq); hipFree(c->p_mu); hipFree(c->p_sd); hipFree(c->p_vz);
-  hipHostFree(c->p_hx); hipHostFree(c->p_hout);
-  c->p_xf = c->p_ks = c->p_vsq = c->p_mu = c->p_sd = c->p_vz = nullptr;
-  c->p_hx = c->p_hout = nullptr;
-  c->p_cols = c->p_np = 0;
-  c->p_d = c->p_nt = 0;
-}
-
-static void free_psurf(gpf_ctx* c) {
-  hipFree(c->s_t); hipFree(c->s_cmp); hipFree(c->s_y); hipFree(c->s_p); hipFree(c->s_info); hipFree(c->s_ok);
-  c->s_t = c->s_cmp = c->s_y = c->s_p = nullptr;
-  c->s_info = nullptr;
-  c->s_ok = nullptr;
-  c->s_rows = 0;
-  c->s_e = 0;
-}
-
-// Device buffers of gpf_predict / gpf_prob_surface are kept for the next call unless larger
-// than GPF_PREDICT_KEEP_MB (default 2048): a one-off large call must not hold HBM that would
-// starve the next factorisation's or hull's allocations
-static double keep_bytes(const Knobs& k) { return (k.predict_keep_mb.set ? k.predict_keep_mb.f : 2048.0) * 1048576.0; }
 
 static void free_work(gpf_ctx* c) {
   clear_graphs(c);
-  free_pred(c);
-  free_psurf(c);
+  for (KeptSet& k : c->kept) k.release();
   hipHostFree(c->h_ls); hipHostFree(c->h_loss); hipHostFree(c->h_info);
   c->h_ls = c->h_loss = nullptr;
   c->h_info = nullptr;
@@ -650,6 +602,46 @@ static int particle_status(gpf_ctx* c, int q) {
   return GPF_OK;
 }
 
+// ---- around the kept sets: what every posterior entry point checks before it allocates ----
+// n length scales, finite and > 0 (fn: the entry point, for the message)
+static int check_ls(gpf_ctx* c, const char* fn, const double* ls, size_t n) {
+  for (size_t i = 0; i < n; ++i)
+    if (!(ls[i] > 0.0) || !std::isfinite(ls[i])) {
+      c->err = std::string(fn) + ": length scales must be finite and > 0";
+      return GPF_BAD_ARG;
+    }
+  return GPF_OK;
+}
+
+// The memory budget of a call's own buffers, half of the free device memory (fr, for the message):
+// queried with `set` given back first (null: as things stand), so what the set held counts as free
+struct Budget {
+  double half = 0.0;
+  size_t fr = 0;
+};
+static int half_free(gpf_ctx* c, KeptSet* set, Budget* b) {
+  if (set) {
+    GPF_HIP(c, hipStreamSynchronize(c->stream));
+    set->release();
+  }
+  size_t tot = 0;
+  GPF_HIP(c, hipMemGetInfo(&b->fr, &tot));
+  b->half = 0.5 * (double)b->fr;
+  return GPF_OK;
+}
+
+// The largest multiple of the tile up to hi for which ok(multiple) holds (ok holds up to some size
+// and not beyond), 0 if none: the "largest M that fits" of the budget messages
+template <typename F>
+static int64_t largest_tiled(int64_t hi, F ok) {
+  int64_t fit = 0;
+  for (int64_t lo = 0, h = hi / T; lo < h;) {
+    const int64_t mid = (lo + h + 1) / 2;
+    if (ok(mid * T)) fit = mid * T, lo = mid; else h = mid - 1;
+  }
+  return fit;
+}
+
 extern "C" {
 
 #ifndef GPF_BUILD_INFO
@@ -917,6 +909,31 @@ static int factor_single(gpf_ctx* c, const double* ls, double** alpha_out, const
   return rc;
 }
 
+// gpf_predict's kept buffers
+enum PredBuf {
+  PRED_XF = 0,  // the chunk's query coordinates, d x Cp
+  PRED_KS,      // K_s, Np x Cp
+  PRED_VSQ,     // per row tile of V = U K_s: the partials of sd and of mu = V^T z (gpf::k_predict_vsq), nt x Cp each
+  PRED_VZ,
+  PRED_MU,      // Cp each
+  PRED_SD,
+  PRED_HX,      // pinned staging: the coordinates, (mu | sd)
+  PRED_HOUT,
+  PRED_NBUF
+};
+constexpr unsigned PRED_PINNED = 1u << PRED_HX | 1u << PRED_HOUT;
+
+static SetPlan pred_plan(const gpf_ctx* c, int64_t Cp) {
+  SetPlan p{};
+  const size_t C = (size_t)Cp;
+  p.bytes[PRED_XF] = p.bytes[PRED_HX] = (size_t)c->d * C * 8;
+  p.bytes[PRED_KS] = (size_t)c->Npad * C * 8;
+  p.bytes[PRED_VSQ] = p.bytes[PRED_VZ] = (size_t)c->nt * C * 8;
+  p.bytes[PRED_MU] = p.bytes[PRED_SD] = C * 8;
+  p.bytes[PRED_HOUT] = 2 * C * 8;
+  return p;
+}
+
 int gpf_predict(gpf_ctx* c, const double* ls, const double* xfit, int64_t M, int64_t batch, double* mu,
                 double* sd) {
   if (!c) return GPF_BAD_ARG;
@@ -931,46 +948,34 @@ int gpf_predict(gpf_ctx* c, const double* ls, const double* xfit, int64_t M, int
   // own host memory, GP_func.py:28-30; results do not depend on it). Sized before the
   // factorisation is queued, so that a (re)allocation never waits for it; free memory is only
   // queried when the kept buffers are too small.
-  // the factorisation workspace first: a (re)allocation there frees the query buffers too
+  // the factorisation workspace first: a (re)allocation there frees the kept sets too
   const Knobs knobs = Knobs::from_env();
   if (int rw = ensure_work(c, 1, knobs)) return rw;
+  KeptSet& ks = c->kept[KEPT_PRED];
   const int64_t Np = c->Npad;
   int64_t chunk = std::min<int64_t>(std::max<int64_t>(std::max<int64_t>(batch, 1), 16384), M);
   int64_t Cp = ((chunk + T - 1) / T) * T;
-  const bool fits = c->p_cols >= Cp && c->p_np == Np && c->p_d == c->d && c->p_nt == c->nt;
-  if (!fits) {
-    size_t fr = 0, tot = 0;
-    GPF_HIP(c, hipMemGetInfo(&fr, &tot));
-    const int64_t per_col = (Np + 2 * c->nt) * 8;
-    const int64_t maxcols = std::max<int64_t>(T, (int64_t)((double)fr * 0.5 / (double)per_col));
-    chunk = std::min<int64_t>(chunk, maxcols);
-    Cp = ((chunk + T - 1) / T) * T;
-  }
   // buffers kept from the previous call when they are large enough (a hipMalloc/hipFree of the
   // Np x Cp cross-covariance per call cost ~1 ms of the call's wall time); pinned host staging
   // for the query coordinates and the outputs (pageable copies stage through a bounce buffer)
-  if (c->p_cols < Cp || c->p_np != Np || c->p_d != c->d || c->p_nt != c->nt) {
-    GPF_HIP(c, hipStreamSynchronize(c->stream));
-    free_pred(c);
-    GPF_HIP(c, hipMalloc(&c->p_xf, (size_t)c->d * Cp * 8));
-    GPF_HIP(c, hipMalloc(&c->p_ks, (size_t)Np * Cp * 8));
-    GPF_HIP(c, hipMalloc(&c->p_vsq, (size_t)c->nt * Cp * 8));
-    GPF_HIP(c, hipMalloc(&c->p_vz, (size_t)c->nt * Cp * 8));
-    GPF_HIP(c, hipMalloc(&c->p_mu, (size_t)Cp * 8));
-    GPF_HIP(c, hipMalloc(&c->p_sd, (size_t)Cp * 8));
-    GPF_HIP(c, hipHostMalloc((void**)&c->p_hx, (size_t)c->d * Cp * 8, hipHostMallocDefault));
-    GPF_HIP(c, hipHostMalloc((void**)&c->p_hout, (size_t)2 * Cp * 8, hipHostMallocDefault));
-    c->p_cols = Cp;
-    c->p_np = Np;
-    c->p_d = c->d;
-    c->p_nt = c->nt;
+  SetPlan p = pred_plan(c, Cp);
+  if (!ks.fits(p.bytes, PRED_NBUF)) {
+    Budget bg;
+    if (int rb = half_free(c, nullptr, &bg)) return rb;
+    const int64_t per_col = (Np + 2 * c->nt) * 8;
+    const int64_t maxcols = std::max<int64_t>(T, (int64_t)(bg.half / (double)per_col));
+    chunk = std::min<int64_t>(chunk, maxcols);
+    Cp = ((chunk + T - 1) / T) * T;
+    p = pred_plan(c, Cp);
+    if (!ks.fits(p.bytes, PRED_NBUF))
+      if (int rg = ks.regrow(c, p.bytes, PRED_PINNED, PRED_NBUF)) return rg;
   }
   // (Two overlaps of V = U K_s with the single-particle factorisation were built and measured in
   // round 4 — V's row tiles on a low-priority side stream behind each factor launch, and the same
   // with the CUs partitioned by stream CU masks — and removed: the factorisation's latency-bound
   // chain needs the whole chip, profiles/r4/ab_r4g_summary.txt, ab_pred_cumask.txt.)
-  double *d_xf = c->p_xf, *d_ks = c->p_ks, *d_vsq = c->p_vsq, *d_vz = c->p_vz, *d_mu = c->p_mu, *d_sd = c->p_sd;
-  double* hx = c->p_hx;
+  double *d_xf = ks.as(PRED_XF), *d_ks = ks.as(PRED_KS), *d_vsq = ks.as(PRED_VSQ), *d_vz = ks.as(PRED_VZ);
+  double *d_mu = ks.as(PRED_MU), *d_sd = ks.as(PRED_SD), *hx = ks.as(PRED_HX), *hout = ks.as(PRED_HOUT);
   const double* d_z = c->d_yb;  // z = U y of particle slot 0
   auto stage_chunk = [&](int64_t s0, int64_t m) -> int {
     for (int k = 0; k < c->d; ++k) std::memcpy(hx + (size_t)k * Cp, xfit + (size_t)k * M + s0, (size_t)m * 8);
@@ -1012,8 +1017,8 @@ int gpf_predict(gpf_ctx* c, const double* ls, const double* xfit, int64_t M, int
                          (int)m, d_vz, (int)Cp, d_vsq, d_mu, d_sd);
     });
     if (rc) break;
-    if (hipMemcpyAsync(c->p_hout, d_mu, (size_t)m * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-        hipMemcpyAsync(c->p_hout + Cp, d_sd, (size_t)m * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+    if (hipMemcpyAsync(hout, d_mu, (size_t)m * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipMemcpyAsync(hout + Cp, d_sd, (size_t)m * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
         hipStreamSynchronize(c->stream) != hipSuccess) {
       rc = GPF_HIP_ERROR;
       c->err = "gpf_predict: copy back failed";
@@ -1023,80 +1028,106 @@ int gpf_predict(gpf_ctx* c, const double* ls, const double* xfit, int64_t M, int
       rc = particle_status(c, 0);
       if (rc) break;
     }
-    std::memcpy(mu + s, c->p_hout, (size_t)m * 8);
-    std::memcpy(sd + s, c->p_hout + Cp, (size_t)m * 8);
+    std::memcpy(mu + s, hout, (size_t)m * 8);
+    std::memcpy(sd + s, hout + Cp, (size_t)m * 8);
   }
   hipStreamSynchronize(c->stream);
   if (c->prof) harvest(c);
   // keep the query-chunk buffers for the next call only while they are modest (a huge batch_size
   // can size them up to half of free HBM; see keep_bytes)
-  if ((double)c->p_np * (double)c->p_cols * 8.0 > keep_bytes(knobs)) free_pred(c);
+  ks.trim(knobs);
   return rc;
 }
 
-// One set of gpf_predict_cov's device buffers (the context keeps two: gpf_predict_cov's own and
-// gpf_posterior_draws')
-struct PcovBufs {
-  double *xf, *ks, *v, *cov, *vsq, *vz, *mu, *hx;
+// gpf_predict_cov's kept buffers, and gpf_posterior_draws': a set like it with its own behind
+enum PcovBuf {
+  PCOV_XF = 0,  // the query coordinates, d x Cp
+  PCOV_KS,      // K_s and V = U K_s, Np x Cp each
+  PCOV_V,
+  PCOV_COV,     // Sigma, Cp x Cp
+  PCOV_VSQ,     // k_predict_v's partials, nt x Cp each
+  PCOV_VZ,
+  PCOV_MU,      // (mu | sd), 2 Cp
+  PCOV_HX,      // pinned staging: the coordinates, the mean
+  PCOV_HMU,
+  PCOV_NBUF
 };
+enum PdrawBuf {
+  PDRAW_L = PCOV_NBUF,  // Sigma's factor L, Cp x Cp
+  PDRAW_Z,              // the normals and the draws, Sp x Cp each
+  PDRAW_DR,
+  PDRAW_U,              // the dense factorisation's U_JJ strip (dense_chol_strip_bytes)
+  PDRAW_NBUF
+};
+constexpr unsigned PCOV_PINNED = 1u << PCOV_HX | 1u << PCOV_HMU;
 
-// gpf_predict_cov's device pipeline, queued on the context's stream: the single-particle
-// factorisation, K_s and K_ss, V = U K_s with the mean's partials, the mean, Sigma's lower tiles and
-// the mirror copy. Leaves mu in b.mu and Sigma in b.cov (leading dimension Cp: symmetric, padded
+static SetPlan pcov_plan(const gpf_ctx* c, int64_t Cp) {
+  SetPlan p{};
+  const size_t C = (size_t)Cp;
+  p.bytes[PCOV_XF] = p.bytes[PCOV_HX] = (size_t)c->d * C * 8;
+  p.bytes[PCOV_KS] = p.bytes[PCOV_V] = (size_t)c->Npad * C * 8;
+  p.bytes[PCOV_COV] = C * C * 8;
+  p.bytes[PCOV_VSQ] = p.bytes[PCOV_VZ] = (size_t)c->nt * C * 8;
+  p.bytes[PCOV_MU] = 2 * C * 8;
+  p.bytes[PCOV_HMU] = C * 8;
+  p.total = device_bytes(p.bytes, PCOV_PINNED, PCOV_NBUF);
+  return p;
+}
+
+// gpf_predict_cov's device pipeline, queued on the context's stream over the buffer set bufs (PCOV_*):
+// the single-particle factorisation, K_s and K_ss, V = U K_s with the mean's partials, the mean, Sigma's
+// lower tiles and the mirror copy. Leaves mu in PCOV_MU and Sigma in PCOV_COV (leading dimension Cp: symmetric, padded
 // diagonal 1, padding 0). gpf_posterior_draws runs the same launches in the same order, so its mean
 // is bitwise gpf_predict_cov's.
 static int pcov_enqueue(gpf_ctx* c, const Knobs& knobs, const double* ls, const double* xfit, int64_t M, int64_t Cp,
-                        const PcovBufs& b) {
+                        void* const* bufs) {
+  auto buf = [&](int i) { return (double*)bufs[i]; };
+  double *xf = buf(PCOV_XF), *ks = buf(PCOV_KS), *v = buf(PCOV_V), *cov = buf(PCOV_COV), *vsq = buf(PCOV_VSQ);
+  double *vz = buf(PCOV_VZ), *mu = buf(PCOV_MU), *hx = buf(PCOV_HX);
   const int64_t Np = c->Npad;
   const int nqt = (int)(Cp / T);
   // the kept buffers may be wider than this call needs: every matrix of the call uses the leading
   // dimension Cp of this call's padded M, so the results do not depend on what an earlier call left
   std::memcpy(c->h_ls, ls, (size_t)c->d * 8);
   GPF_HIP(c, hipMemcpyAsync(c->d_ls, c->h_ls, (size_t)c->d * 8, hipMemcpyHostToDevice, c->stream));
-  for (int k = 0; k < c->d; ++k) std::memcpy(b.hx + (size_t)k * Cp, xfit + (size_t)k * M, (size_t)M * 8);
-  GPF_HIP(c, hipMemcpyAsync(b.xf, b.hx, (size_t)c->d * Cp * 8, hipMemcpyHostToDevice, c->stream));
+  for (int k = 0; k < c->d; ++k) std::memcpy(hx + (size_t)k * Cp, xfit + (size_t)k * M, (size_t)M * 8);
+  GPF_HIP(c, hipMemcpyAsync(xf, hx, (size_t)c->d * Cp * 8, hipMemcpyHostToDevice, c->stream));
   int rc = factor_single_async(c, nullptr, nullptr, knobs);
   if (rc) return rc;
   // K_s (Np x Cp, zero rows / columns past N / M) and K_ss into Sigma's buffer (zero past M)
   rc = launch(c, PC_PREDK, 8.0 * Np * Cp + 8.0 * Cp * Cp, [&] {
-    gpf::launch_cross_cov(c->stream, (int)c->N, (int)M, (int)Np, (int)Cp, c->d, c->d_x, (int)c->N, b.xf, (int)Cp, c->d_ls,
-                          b.ks, Cp);
-    gpf::launch_cross_cov(c->stream, (int)M, (int)M, (int)Cp, (int)Cp, c->d, b.xf, (int)Cp, b.xf, (int)Cp, c->d_ls,
-                          b.cov, Cp);
+    gpf::launch_cross_cov(c->stream, (int)c->N, (int)M, (int)Np, (int)Cp, c->d, c->d_x, (int)c->N, xf, (int)Cp, c->d_ls,
+                          ks, Cp);
+    gpf::launch_cross_cov(c->stream, (int)M, (int)M, (int)Cp, (int)Cp, c->d, xf, (int)Cp, xf, (int)Cp, c->d_ls,
+                          cov, Cp);
   });
   // V = U K_s, stored (flops as gpf_predict counts them), and its per-column partials
   const double vflops = 2.0 * T * T * (double)Cp * ((double)c->nt * (c->nt + 1) / 2) - (double)T * T * Cp * c->nt;
   if (!rc)
     rc = launch(c, PC_PRED, vflops, [&] {
-      hipLaunchKernelGGL(gpf::k_predict_v, dim3(nqt, c->nt), dim3(gpf::Geo<T>::NTH), 0, c->stream, (int)Np, c->d_U, b.ks,
-                         (int)Cp, b.vsq, c->d_yb, b.vz, b.v);
+      hipLaunchKernelGGL(gpf::k_predict_v, dim3(nqt, c->nt), dim3(gpf::Geo<T>::NTH), 0, c->stream, (int)Np, c->d_U, ks,
+                         (int)Cp, vsq, c->d_yb, vz, v);
     });
   if (!rc)
     rc = launch(c, PC_LOSS, 0.0, [&] {
       hipLaunchKernelGGL(gpf::k_predict_out, dim3((unsigned)((M + NTHR - 1) / NTHR)), dim3(NTHR), 0, c->stream, c->nt, (int)M,
-                         b.vz, (int)Cp, b.vsq, b.mu, b.mu + Cp);
+                         vz, (int)Cp, vsq, mu, mu + Cp);
     });
   // Sigma's lower tiles, 2 T^2 Np flops each (the diagonal tiles counted in full, as k_lml_grad's):
   // Np Cp^2 for the lower half plus Np Cp T for the diagonal tiles
   const int ntile = nqt * (nqt + 1) / 2;
   if (!rc)
     rc = launch(c, PC_PRED, 2.0 * T * T * (double)Np * ntile, [&] {
-      hipLaunchKernelGGL(gpf::k_post_cov, dim3((unsigned)ntile), dim3(gpf::Geo<T>::NTH), 0, c->stream, (int)Np, nqt, b.v,
-                         (int)Cp, b.cov, Cp);
+      hipLaunchKernelGGL(gpf::k_post_cov, dim3((unsigned)ntile), dim3(gpf::Geo<T>::NTH), 0, c->stream, (int)Np, nqt, v,
+                         (int)Cp, cov, Cp);
     });
   const int nmb = (int)((M + gpf::MIR_B - 1) / gpf::MIR_B);
   if (!rc)
     rc = launch(c, PC_PREDK, 8.0 * (double)M * M, [&] {
-      hipLaunchKernelGGL(gpf::k_mirror_lower, dim3((unsigned)(nmb * (nmb + 1) / 2)), dim3(NTHR), 0, c->stream, (int)M, b.cov,
+      hipLaunchKernelGGL(gpf::k_mirror_lower, dim3((unsigned)(nmb * (nmb + 1) / 2)), dim3(NTHR), 0, c->stream, (int)M, cov,
                          Cp);
     });
   return rc;
-}
-
-// Device bytes gpf_predict_cov needs for Cp (padded) query columns: K_s and V (Np x Cp each), Sigma
-// (Cp x Cp), the vsq / vz partials (nt x Cp each), the coordinates and (mu | sd)
-static double pcov_bytes(const gpf_ctx* c, double Cp) {
-  return 8.0 * (2.0 * (double)c->Npad * Cp + Cp * Cp + (2.0 * c->nt + c->d + 2.0) * Cp);
 }
 
 int gpf_predict_cov(gpf_ctx* c, const double* ls, const double* xfit, int64_t M, double* mu, double* cov) {
@@ -1105,8 +1136,7 @@ int gpf_predict_cov(gpf_ctx* c, const double* ls, const double* xfit, int64_t M,
   if (M < 0) return bad_arg(c, "gpf_predict_cov: M < 0");
   if (!ls) return bad_arg(c, "gpf_predict_cov: null length scales");
   if (M > 0 && (!xfit || !mu || !cov)) return bad_arg(c, "gpf_predict_cov: null buffer");
-  for (int k = 0; k < c->d; ++k)
-    if (!(ls[k] > 0.0) || !std::isfinite(ls[k])) return bad_arg(c, "gpf_predict_cov: length scales must be finite and > 0");
+  if (int rl = check_ls(c, "gpf_predict_cov", ls, (size_t)c->d)) return rl;
   if (M > (int64_t)1 << 24) return bad_arg(c, "gpf_predict_cov: M > 2^24 (Sigma is dense: M x M doubles)");
   if (M == 0) return GPF_OK;
   hipSetDevice(c->device);
@@ -1114,44 +1144,25 @@ int gpf_predict_cov(gpf_ctx* c, const double* ls, const double* xfit, int64_t M,
   // the factorisation workspace first: a (re)allocation there frees the query buffers too
   const Knobs knobs = Knobs::from_env();
   if (int rw = ensure_work(c, 1, knobs)) return rw;
-  const int64_t Np = c->Npad;
-  const int nqt = (int)((M + T - 1) / T);
-  const int64_t Cp = (int64_t)nqt * T;
-  if (c->c_cols < Cp || c->c_np != Np || c->c_d != c->d || c->c_nt != c->nt) {
-    GPF_HIP(c, hipStreamSynchronize(c->stream));
-    free_pcov(c);
+  KeptSet& ks = c->kept[KEPT_PCOV];
+  const int64_t Cp = ((M + T - 1) / T) * T;
+  const SetPlan p = pcov_plan(c, Cp);
+  if (!ks.fits(p.bytes, PCOV_NBUF)) {
     // no chunking over M: K_s, V and Sigma must fit half of free HBM together
-    size_t fr = 0, tot = 0;
-    GPF_HIP(c, hipMemGetInfo(&fr, &tot));
-    const double budget = 0.5 * (double)fr;
-    if (pcov_bytes(c, (double)Cp) > budget) {
-      int64_t fit = 0;  // the largest multiple of the tile that fits (pcov_bytes grows with Cp)
-      for (int64_t lo = 0, hi = Cp / T; lo < hi;) {
-        const int64_t mid = (lo + hi + 1) / 2;
-        if (pcov_bytes(c, (double)(mid * T)) <= budget) fit = mid * T, lo = mid; else hi = mid - 1;
-      }
+    Budget bg;
+    if (int rb = half_free(c, &ks, &bg)) return rb;
+    if (p.total > bg.half) {
+      const int64_t fit = largest_tiled(Cp, [&](int64_t cols) { return pcov_plan(c, cols).total <= bg.half; });
       c->err = "gpf_predict_cov: K_s, V and Sigma for M=" + std::to_string(M) + " at N=" + std::to_string(c->N) +
-               " need " + std::to_string((long long)(pcov_bytes(c, (double)Cp) / 1048576.0)) + " MiB, more than half of the free " +
-               std::to_string((long long)(fr / 1048576)) + " MiB of device memory; the largest M that fits is " + std::to_string(fit);
+               " need " + std::to_string((long long)(p.total / 1048576.0)) + " MiB, more than half of the free " +
+               std::to_string((long long)(bg.fr / 1048576)) + " MiB of device memory; the largest M that fits is " + std::to_string(fit);
       return GPF_BAD_ARG;
     }
-    GPF_HIP(c, hipMalloc(&c->c_xf, (size_t)c->d * Cp * 8));
-    GPF_HIP(c, hipMalloc(&c->c_ks, (size_t)Np * Cp * 8));
-    GPF_HIP(c, hipMalloc(&c->c_v, (size_t)Np * Cp * 8));
-    GPF_HIP(c, hipMalloc(&c->c_cov, (size_t)Cp * Cp * 8));
-    GPF_HIP(c, hipMalloc(&c->c_vsq, (size_t)c->nt * Cp * 8));
-    GPF_HIP(c, hipMalloc(&c->c_vz, (size_t)c->nt * Cp * 8));
-    GPF_HIP(c, hipMalloc(&c->c_mu, (size_t)2 * Cp * 8));
-    GPF_HIP(c, hipHostMalloc((void**)&c->c_hx, (size_t)c->d * Cp * 8, hipHostMallocDefault));
-    GPF_HIP(c, hipHostMalloc((void**)&c->c_hmu, (size_t)Cp * 8, hipHostMallocDefault));
-    c->c_cols = Cp;
-    c->c_np = Np;
-    c->c_d = c->d;
-    c->c_nt = c->nt;
+    if (int rg = ks.regrow(c, p.bytes, PCOV_PINNED, PCOV_NBUF)) return rg;
   }
-  const PcovBufs bufs{c->c_xf, c->c_ks, c->c_v, c->c_cov, c->c_vsq, c->c_vz, c->c_mu, c->c_hx};
-  int rc = pcov_enqueue(c, knobs, ls, xfit, M, Cp, bufs);
-  if (!rc && hipMemcpyAsync(c->c_hmu, c->c_mu, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
+  double *d_mu = ks.as(PCOV_MU), *hmu = ks.as(PCOV_HMU);
+  int rc = pcov_enqueue(c, knobs, ls, xfit, M, Cp, ks.p);
+  if (!rc && hipMemcpyAsync(hmu, d_mu, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
     rc = GPF_HIP_ERROR;
     c->err = "gpf_predict_cov: copy back failed";
   }
@@ -1162,8 +1173,8 @@ int gpf_predict_cov(gpf_ctx* c, const double* ls, const double* xfit, int64_t M,
   // the factorisation's status before anything reaches the caller's buffers
   if (!rc) rc = particle_status(c, 0);
   if (!rc) {
-    std::memcpy(mu, c->c_hmu, (size_t)M * 8);
-    if (hipMemcpy2DAsync(cov, (size_t)M * 8, c->c_cov, (size_t)Cp * 8, (size_t)M * 8, (size_t)M, hipMemcpyDeviceToHost,
+    std::memcpy(mu, hmu, (size_t)M * 8);
+    if (hipMemcpy2DAsync(cov, (size_t)M * 8, ks.as(PCOV_COV), (size_t)Cp * 8, (size_t)M * 8, (size_t)M, hipMemcpyDeviceToHost,
                          c->stream) != hipSuccess ||
         hipStreamSynchronize(c->stream) != hipSuccess) {
       rc = GPF_HIP_ERROR;
@@ -1171,12 +1182,12 @@ int gpf_predict_cov(gpf_ctx* c, const double* ls, const double* xfit, int64_t M,
     }
   }
   if (c->prof) harvest(c);
-  if (pcov_bytes(c, (double)c->c_cols) > keep_bytes(knobs)) free_pcov(c);
+  ks.trim(knobs);
   return rc;
 }
 
 // ---- linear functionals of the posterior (gpf_linear.hip) ----
-// gpf_predict_linear's device buffers (gpf_ctx::l_buf)
+// gpf_predict_linear's kept buffers
 enum LinBuf {
   LIN_WRAW = 0,  // the weights as given, R x M
   LIN_WT,        // Wt = A^T, Mp x Rp, zero padded
@@ -1193,7 +1204,6 @@ enum LinBuf {
   LIN_PART,      // the partial tiles of the product in flight
   LIN_NBUF
 };
-static_assert(LIN_NBUF <= 16, "gpf_ctx::l_buf");
 
 // The shape of one gpf_predict_linear call: the padded sizes, the query points per pass and the bytes
 // of every buffer
@@ -1233,14 +1243,8 @@ static LinPlan lin_plan(const gpf_ctx* c, int64_t M, int R, int64_t Cc) {
   p.bytes[LIN_VSQ] = p.bytes[LIN_VZ] = (size_t)p.nt * Rp * 8;
   p.bytes[LIN_MU] = 2 * Rp * 8;
   p.bytes[LIN_PART] = ptiles * gpf::LIN_TT * 8;
-  for (int i = 0; i < LIN_NBUF; ++i) p.total += (double)p.bytes[i];
+  p.total = device_bytes(p.bytes, 0, LIN_NBUF);
   return p;
-}
-
-static bool lin_fits_kept(const gpf_ctx* c, const LinPlan& p) {
-  for (int i = 0; i < LIN_NBUF; ++i)
-    if (p.bytes[i] > c->l_cap[i]) return false;
-  return true;
 }
 
 // One skinny product behind the stream: the partial tiles of `tiles` output tiles over dt depth
@@ -1364,8 +1368,7 @@ int gpf_predict_linear(gpf_ctx* c, const double* ls, const double* xfit, int64_t
   if (M < 0 || R < 0 || chunk < 0) return bad_arg(c, "gpf_predict_linear: M, R and chunk must be >= 0");
   if (!ls) return bad_arg(c, "gpf_predict_linear: null length scales");
   if (M > 0 && R > 0 && (!xfit || !w || !mean || !cov)) return bad_arg(c, "gpf_predict_linear: null buffer");
-  for (int k = 0; k < c->d; ++k)
-    if (!(ls[k] > 0.0) || !std::isfinite(ls[k])) return bad_arg(c, "gpf_predict_linear: length scales must be finite and > 0");
+  if (int rl = check_ls(c, "gpf_predict_linear", ls, (size_t)c->d)) return rl;
   if (M > (int64_t)1 << 30) return bad_arg(c, "gpf_predict_linear: M > 2^30");
   if (R > 1 << 14) return bad_arg(c, "gpf_predict_linear: R > 16384");
   if (M == 0 || R == 0) return GPF_OK;
@@ -1380,38 +1383,29 @@ int gpf_predict_linear(gpf_ctx* c, const double* ls, const double* xfit, int64_t
   // leading dimension and the byte offsets of the streamed panels stay well inside 32 bits)
   int64_t Cc = std::min<int64_t>(chunk > 0 ? chunk : 16384, 65536);
   Cc = ((Cc + T - 1) / T) * T;
+  KeptSet& ks = c->kept[KEPT_LIN];
   LinPlan p = lin_plan(c, M, R, Cc);
-  if (!lin_fits_kept(c, p)) {
-    GPF_HIP(c, hipStreamSynchronize(c->stream));
-    free_plin(c);
-    size_t fr = 0, tot = 0;
-    GPF_HIP(c, hipMemGetInfo(&fr, &tot));
-    const double budget = 0.5 * (double)fr;
-    while (p.total > budget && p.Cc > T) {  // fewer query points per pass
+  if (!ks.fits(p.bytes, LIN_NBUF)) {
+    Budget bg;
+    if (int rb = half_free(c, &ks, &bg)) return rb;
+    while (p.total > bg.half && p.Cc > T) {  // fewer query points per pass
       Cc = std::max<int64_t>(T, ((p.Cc / 2 + T - 1) / T) * T);
       p = lin_plan(c, M, R, Cc);
     }
-    if (p.total > budget) {
-      int64_t fit = 0;  // the largest multiple of the tile that fits at this R (the bytes grow with M)
-      for (int64_t lo = 0, hi = p.Mp / T; lo < hi;) {
-        const int64_t mid = (lo + hi + 1) / 2;
-        if (lin_plan(c, mid * T, R, T).total <= budget) fit = mid * T, lo = mid; else hi = mid - 1;
-      }
+    if (p.total > bg.half) {
+      const int64_t fit = largest_tiled(p.Mp, [&](int64_t m) { return lin_plan(c, m, R, T).total <= bg.half; });
       c->err = "gpf_predict_linear: the weights, the coordinates and the operands for M=" + std::to_string(M) + ", R=" +
                std::to_string(R) + " at N=" + std::to_string(c->N) + " need " + std::to_string((long long)(p.total / 1048576.0)) +
-               " MiB at 128 query points per pass, more than half of the free " + std::to_string((long long)(fr / 1048576)) +
+               " MiB at 128 query points per pass, more than half of the free " + std::to_string((long long)(bg.fr / 1048576)) +
                " MiB of device memory; the largest M that fits at this R is " + std::to_string(fit);
       return GPF_BAD_ARG;
     }
-    for (int i = 0; i < LIN_NBUF; ++i) {
-      GPF_HIP(c, hipMalloc(&c->l_buf[i], p.bytes[i]));
-      c->l_cap[i] = p.bytes[i];
-    }
+    if (int rg = ks.regrow(c, p.bytes, 0, LIN_NBUF)) return rg;
   }
   const int Rp = p.Rp;
-  double *Q = (double*)c->l_buf[LIN_Q], *S = (double*)c->l_buf[LIN_COV], *mu = (double*)c->l_buf[LIN_MU];
+  double *Q = ks.as(LIN_Q), *S = ks.as(LIN_COV), *mu = ks.as(LIN_MU);
   hipStream_t st = c->stream;
-  int rc = lin_enqueue(c, knobs, c->l_buf, p, ls, xfit, M, w, R);
+  int rc = lin_enqueue(c, knobs, ks.p, p, ls, xfit, M, w, R);
   if (hipStreamSynchronize(st) != hipSuccess && !rc) {
     rc = GPF_HIP_ERROR;
     c->err = "gpf_predict_linear: synchronisation failed";
@@ -1429,9 +1423,7 @@ int gpf_predict_linear(gpf_ctx* c, const double* ls, const double* xfit, int64_t
     }
   }
   if (c->prof) harvest(c);
-  double held = 0.0;
-  for (int i = 0; i < LIN_NBUF; ++i) held += (double)c->l_cap[i];
-  if (held > keep_bytes(knobs)) free_plin(c);
+  ks.trim(knobs);
   return rc;
 }
 
@@ -1496,6 +1488,22 @@ static const char* ladder_arg_error(const double* jitters, int nj) {
   return nullptr;
 }
 
+// gpf_chol_dense's kept buffers
+enum DcholBuf {
+  DCHOL_A = 0,  // the matrix and its factor, np x np each
+  DCHOL_L,
+  DCHOL_U,      // the U_JJ strip (dense_chol_strip_bytes)
+  DCHOL_NBUF
+};
+
+static SetPlan dchol_plan(int64_t np) {
+  SetPlan p{};
+  p.bytes[DCHOL_A] = p.bytes[DCHOL_L] = (size_t)np * np * 8;
+  p.bytes[DCHOL_U] = dense_chol_strip_bytes(np);
+  p.total = device_bytes(p.bytes, 0, DCHOL_NBUF);
+  return p;
+}
+
 int gpf_chol_dense(gpf_ctx* c, const double* A, int64_t n, const double* jitters, int nj, double* L, double* jitter_used,
                    int* tries) {
   if (!c) return GPF_BAD_ARG;
@@ -1511,37 +1519,33 @@ int gpf_chol_dense(gpf_ctx* c, const double* A, int64_t n, const double* jitters
   hipSetDevice(c->device);
   const Knobs knobs = Knobs::from_env();
   const int64_t np = ((n + T - 1) / T) * T;  // rows and leading dimension of this call's matrices
-  const double need = 2.0 * 8.0 * (double)np * np + (double)dense_chol_strip_bytes(np);
-  if ((size_t)np * np * 8 > c->dc_a.cap) {
-    GPF_HIP(c, hipStreamSynchronize(c->stream));
-    free_dchol(c);
-    size_t fr = 0, tot = 0;
-    GPF_HIP(c, hipMemGetInfo(&fr, &tot));
-    if (need > 0.5 * (double)fr) {
-      const int64_t fit = (int64_t)(std::sqrt(0.5 * (double)fr / 16.0) / T) * T - T;
+  KeptSet& ks = c->kept[KEPT_DCHOL];
+  const SetPlan p = dchol_plan(np);
+  if (!ks.fits(p.bytes, DCHOL_NBUF)) {
+    Budget bg;
+    if (int rb = half_free(c, &ks, &bg)) return rb;
+    if (p.total > bg.half) {
+      const int64_t fit = (int64_t)(std::sqrt(bg.half / 16.0) / T) * T - T;
       c->err = "gpf_chol_dense: the matrix and its factor for n=" + std::to_string(n) + " need " +
-               std::to_string((long long)(need / 1048576.0)) + " MiB, more than half of the free " +
-               std::to_string((long long)(fr / 1048576)) + " MiB of device memory; the largest n that fits is " +
+               std::to_string((long long)(p.total / 1048576.0)) + " MiB, more than half of the free " +
+               std::to_string((long long)(bg.fr / 1048576)) + " MiB of device memory; the largest n that fits is " +
                std::to_string(std::max<int64_t>(fit, 0));
       return GPF_BAD_ARG;
     }
+    if (int rg = ks.regrow(c, p.bytes, 0, DCHOL_NBUF)) return rg;
   }
-  int rc = c->dc_a.grow(c, (size_t)np * np * 8, false, true);
-  if (!rc) rc = c->dc_l.grow(c, (size_t)np * np * 8, false, true);
-  if (!rc) rc = c->dc_u.grow(c, dense_chol_strip_bytes(np), false, true);
-  if (rc) return rc;
-  double *dA = c->dc_a.as<double>(), *dL = c->dc_l.as<double>();
+  double *dA = ks.as(DCHOL_A), *dL = ks.as(DCHOL_L);
   // A zero-padded with an identity block; L's tiles above the diagonal are never written by the
   // factorisation: zero for the copy back
   GPF_HIP(c, hipMemsetAsync(dA, 0, (size_t)np * np * 8, c->stream));
   GPF_HIP(c, hipMemsetAsync(dL, 0, (size_t)np * np * 8, c->stream));
   GPF_HIP(c, hipMemcpy2DAsync(dA, (size_t)np * 8, A, (size_t)n * 8, (size_t)n * 8, (size_t)n, hipMemcpyHostToDevice, c->stream));
-  rc = launch(c, PC_PREDK, 8.0 * (double)n * n, [&] {
+  int rc = launch(c, PC_PREDK, 8.0 * (double)n * n, [&] {
     hipLaunchKernelGGL(gpf::k_dc_pad_diag, dim3(1), dim3(T), 0, c->stream, (int)n, (int)np, dA, np);
   });
   double jit = 0.0;
   int tr = 0;
-  if (!rc) rc = dense_chol_ladder(c, dA, dL, c->dc_u.as<double>(), n, np, jitters, nj, &jit, &tr);
+  if (!rc) rc = dense_chol_ladder(c, dA, dL, ks.as(DCHOL_U), n, np, jitters, nj, &jit, &tr);
   if (rc == GPF_OK) {
     if (hipMemcpy2DAsync(L, (size_t)n * 8, dL, (size_t)np * 8, (size_t)n * 8, (size_t)n, hipMemcpyDeviceToHost, c->stream) !=
             hipSuccess ||
@@ -1554,14 +1558,17 @@ int gpf_chol_dense(gpf_ctx* c, const double* A, int64_t n, const double* jitters
   if (rc == GPF_OK || rc == GPF_NOT_PD) *tries = tr;
   hipStreamSynchronize(c->stream);
   if (c->prof) harvest(c);
-  if (need > keep_bytes(knobs)) free_dchol(c);
+  ks.trim(knobs);
   return rc;
 }
 
-// Device bytes gpf_posterior_draws needs: gpf_predict_cov's for Cp columns, the factor L (Cp x Cp),
-// the normals and the draws (Sp x Cp each) and the U_JJ strip
-static double pdraw_bytes(const gpf_ctx* c, double Cp, double Sp) {
-  return pcov_bytes(c, Cp) + 8.0 * (Cp * Cp + 2.0 * Sp * Cp + (double)T * Cp + gpf::DC_JUNK + 1);
+static SetPlan pdraw_plan(const gpf_ctx* c, int64_t Cp, int64_t Sp) {
+  SetPlan p = pcov_plan(c, Cp);
+  p.bytes[PDRAW_L] = (size_t)Cp * Cp * 8;
+  p.bytes[PDRAW_Z] = p.bytes[PDRAW_DR] = (size_t)Sp * Cp * 8;
+  p.bytes[PDRAW_U] = dense_chol_strip_bytes(Cp);
+  p.total = device_bytes(p.bytes, PCOV_PINNED, PDRAW_NBUF);
+  return p;
 }
 
 int gpf_posterior_draws(gpf_ctx* c, const double* ls, const double* xfit, int64_t M, const double* z, int64_t S,
@@ -1578,8 +1585,7 @@ int gpf_posterior_draws(gpf_ctx* c, const double* ls, const double* xfit, int64_
   }
   if (M > 0 && (!xfit || !mu)) return bad_arg(c, "gpf_posterior_draws: null buffer");
   if (M > 0 && S > 0 && (!z || !draws)) return bad_arg(c, "gpf_posterior_draws: null buffer");
-  for (int k = 0; k < c->d; ++k)
-    if (!(ls[k] > 0.0) || !std::isfinite(ls[k])) return bad_arg(c, "gpf_posterior_draws: length scales must be finite and > 0");
+  if (int rl = check_ls(c, "gpf_posterior_draws", ls, (size_t)c->d)) return rl;
   if (M > (int64_t)1 << 24 || S > (int64_t)1 << 24) return bad_arg(c, "gpf_posterior_draws: M or S > 2^24");
   if (M == 0 || S == 0) return GPF_OK;
   hipSetDevice(c->device);
@@ -1587,59 +1593,37 @@ int gpf_posterior_draws(gpf_ctx* c, const double* ls, const double* xfit, int64_
   // the factorisation workspace first: a (re)allocation there frees the query buffers too
   const Knobs knobs = Knobs::from_env();
   if (int rw = ensure_work(c, 1, knobs)) return rw;
-  const int64_t Np = c->Npad;
+  KeptSet& ks = c->kept[KEPT_PDRAW];
   const int nqt = (int)((M + T - 1) / T), nst = (int)((S + T - 1) / T);
   const int64_t Cp = (int64_t)nqt * T, Sp = (int64_t)nst * T;
-  if (c->g_cols < Cp || c->g_rows < Sp || c->g_np != Np || c->g_d != c->d || c->g_nt != c->nt) {
-    GPF_HIP(c, hipStreamSynchronize(c->stream));
-    free_pdraw(c);
+  const SetPlan p = pdraw_plan(c, Cp, Sp);
+  if (!ks.fits(p.bytes, PDRAW_NBUF)) {
     // no chunking over M: everything must fit half of free HBM together
-    size_t fr = 0, tot = 0;
-    GPF_HIP(c, hipMemGetInfo(&fr, &tot));
-    const double budget = 0.5 * (double)fr;
-    if (pdraw_bytes(c, (double)Cp, (double)Sp) > budget) {
-      int64_t fit = 0;  // the largest multiple of the tile that fits with this S
-      for (int64_t lo = 0, hi = Cp / T; lo < hi;) {
-        const int64_t mid = (lo + hi + 1) / 2;
-        if (pdraw_bytes(c, (double)(mid * T), (double)Sp) <= budget) fit = mid * T, lo = mid; else hi = mid - 1;
-      }
+    Budget bg;
+    if (int rb = half_free(c, &ks, &bg)) return rb;
+    if (p.total > bg.half) {
+      const int64_t fit = largest_tiled(Cp, [&](int64_t cols) { return pdraw_plan(c, cols, Sp).total <= bg.half; });
       c->err = "gpf_posterior_draws: K_s, V, Sigma, its factor and the draws for M=" + std::to_string(M) + ", S=" +
                std::to_string(S) + " at N=" + std::to_string(c->N) + " need " +
-               std::to_string((long long)(pdraw_bytes(c, (double)Cp, (double)Sp) / 1048576.0)) + " MiB, more than half of the free " +
-               std::to_string((long long)(fr / 1048576)) + " MiB of device memory; the largest M that fits is " + std::to_string(fit);
+               std::to_string((long long)(p.total / 1048576.0)) + " MiB, more than half of the free " +
+               std::to_string((long long)(bg.fr / 1048576)) + " MiB of device memory; the largest M that fits is " + std::to_string(fit);
       return GPF_BAD_ARG;
     }
-    GPF_HIP(c, hipMalloc(&c->g_xf, (size_t)c->d * Cp * 8));
-    GPF_HIP(c, hipMalloc(&c->g_ks, (size_t)Np * Cp * 8));
-    GPF_HIP(c, hipMalloc(&c->g_v, (size_t)Np * Cp * 8));
-    GPF_HIP(c, hipMalloc(&c->g_cov, (size_t)Cp * Cp * 8));
-    GPF_HIP(c, hipMalloc(&c->g_vsq, (size_t)c->nt * Cp * 8));
-    GPF_HIP(c, hipMalloc(&c->g_vz, (size_t)c->nt * Cp * 8));
-    GPF_HIP(c, hipMalloc(&c->g_mu, (size_t)2 * Cp * 8));
-    GPF_HIP(c, hipMalloc(&c->g_L, (size_t)Cp * Cp * 8));
-    GPF_HIP(c, hipMalloc(&c->g_z, (size_t)Sp * Cp * 8));
-    GPF_HIP(c, hipMalloc(&c->g_dr, (size_t)Sp * Cp * 8));
-    GPF_HIP(c, hipMalloc(&c->g_u, dense_chol_strip_bytes(Cp)));
-    GPF_HIP(c, hipHostMalloc((void**)&c->g_hx, (size_t)c->d * Cp * 8, hipHostMallocDefault));
-    GPF_HIP(c, hipHostMalloc((void**)&c->g_hmu, (size_t)Cp * 8, hipHostMallocDefault));
-    c->g_cols = Cp;
-    c->g_rows = Sp;
-    c->g_np = Np;
-    c->g_d = c->d;
-    c->g_nt = c->nt;
+    if (int rg = ks.regrow(c, p.bytes, PCOV_PINNED, PDRAW_NBUF)) return rg;
   }
+  double *d_mu = ks.as(PCOV_MU), *hmu = ks.as(PCOV_HMU), *d_cov = ks.as(PCOV_COV);
+  double *d_L = ks.as(PDRAW_L), *d_z = ks.as(PDRAW_Z), *d_dr = ks.as(PDRAW_DR);
   // (as in gpf_predict_cov, every matrix of the call uses this call's Cp as its leading dimension)
   // the mean's padding is read by k_draws for the padded columns only: finite, not uninitialised
-  GPF_HIP(c, hipMemsetAsync(c->g_mu, 0, (size_t)Cp * 8, c->stream));
-  const PcovBufs bufs{c->g_xf, c->g_ks, c->g_v, c->g_cov, c->g_vsq, c->g_vz, c->g_mu, c->g_hx};
-  int rc = pcov_enqueue(c, knobs, ls, xfit, M, Cp, bufs);
-  if (!rc && hipMemcpyAsync(c->g_hmu, c->g_mu, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
+  GPF_HIP(c, hipMemsetAsync(d_mu, 0, (size_t)Cp * 8, c->stream));
+  int rc = pcov_enqueue(c, knobs, ls, xfit, M, Cp, ks.p);
+  if (!rc && hipMemcpyAsync(hmu, d_mu, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
     rc = GPF_HIP_ERROR;
     c->err = "gpf_posterior_draws: copy back failed";
   }
   // the normals, zero-padded to Sp x Cp (behind the pipeline's launches on the stream; pageable source)
-  if (!rc && (hipMemsetAsync(c->g_z, 0, (size_t)Sp * Cp * 8, c->stream) != hipSuccess ||
-              hipMemcpy2DAsync(c->g_z, (size_t)Cp * 8, z, (size_t)M * 8, (size_t)M * 8, (size_t)S, hipMemcpyHostToDevice,
+  if (!rc && (hipMemsetAsync(d_z, 0, (size_t)Sp * Cp * 8, c->stream) != hipSuccess ||
+              hipMemcpy2DAsync(d_z, (size_t)Cp * 8, z, (size_t)M * 8, (size_t)M * 8, (size_t)S, hipMemcpyHostToDevice,
                                c->stream) != hipSuccess)) {
     rc = GPF_HIP_ERROR;
     c->err = "gpf_posterior_draws: upload of the normals failed";
@@ -1652,20 +1636,20 @@ int gpf_posterior_draws(gpf_ctx* c, const double* ls, const double* xfit, int64_
   if (!rc) rc = particle_status(c, 0);
   double jit = 0.0;
   int tr = 0;
-  if (!rc && chol) rc = hipMemsetAsync(c->g_L, 0, (size_t)Cp * Cp * 8, c->stream) == hipSuccess ? GPF_OK : GPF_HIP_ERROR;
+  if (!rc && chol) rc = hipMemsetAsync(d_L, 0, (size_t)Cp * Cp * 8, c->stream) == hipSuccess ? GPF_OK : GPF_HIP_ERROR;
   const bool laddered = !rc;
-  if (!rc) rc = dense_chol_ladder(c, c->g_cov, c->g_L, c->g_u, M, Cp, jitters, nj, &jit, &tr);
+  if (!rc) rc = dense_chol_ladder(c, d_cov, d_L, ks.as(PDRAW_U), M, Cp, jitters, nj, &jit, &tr);
   if (!rc)  // 2 T^2 flops per 128-deep step of a tile, depth 128 (I + 1)
     rc = launch(c, PC_PRED, 2.0 * T * T * (double)T * nst * ((double)nqt * (nqt + 1) / 2), [&] {
-      hipLaunchKernelGGL(gpf::k_draws, dim3(nst, nqt), dim3(gpf::DNTH), 0, c->stream, nqt, c->g_z, (int)Cp, c->g_L, (int)Cp,
-                         c->g_mu, c->g_dr);
+      hipLaunchKernelGGL(gpf::k_draws, dim3(nst, nqt), dim3(gpf::DNTH), 0, c->stream, nqt, d_z, (int)Cp, d_L, (int)Cp,
+                         d_mu, d_dr);
     });
   if (!rc) {
     // nothing of size M x M leaves the device unless the caller asks for the factor
-    bool ok = hipMemcpy2DAsync(draws, (size_t)M * 8, c->g_dr, (size_t)Cp * 8, (size_t)M * 8, (size_t)S, hipMemcpyDeviceToHost,
+    bool ok = hipMemcpy2DAsync(draws, (size_t)M * 8, d_dr, (size_t)Cp * 8, (size_t)M * 8, (size_t)S, hipMemcpyDeviceToHost,
                                c->stream) == hipSuccess;
     if (ok && chol)
-      ok = hipMemcpy2DAsync(chol, (size_t)M * 8, c->g_L, (size_t)Cp * 8, (size_t)M * 8, (size_t)M, hipMemcpyDeviceToHost,
+      ok = hipMemcpy2DAsync(chol, (size_t)M * 8, d_L, (size_t)Cp * 8, (size_t)M * 8, (size_t)M, hipMemcpyDeviceToHost,
                             c->stream) == hipSuccess;
     if (!ok || hipStreamSynchronize(c->stream) != hipSuccess) {
       rc = GPF_HIP_ERROR;
@@ -1673,18 +1657,18 @@ int gpf_posterior_draws(gpf_ctx* c, const double* ls, const double* xfit, int64_
     }
   }
   if (!rc) {
-    std::memcpy(mu, c->g_hmu, (size_t)M * 8);
+    std::memcpy(mu, hmu, (size_t)M * 8);
     *jitter_used = jit;
   }
   if (laddered && (rc == GPF_OK || rc == GPF_NOT_PD)) *tries = tr;
   hipStreamSynchronize(c->stream);
   if (c->prof) harvest(c);
-  if (pdraw_bytes(c, (double)c->g_cols, (double)c->g_rows) > keep_bytes(knobs)) free_pdraw(c);
+  ks.trim(knobs);
   return rc;
 }
 
 // ---- the posterior conditioned on measured linear functionals (gpf_conditioned.hip) ----
-// gpf_predict_conditioned's device buffers (gpf_ctx::n_buf): the LIN_* set first, then its own
+// gpf_predict_conditioned's kept buffers: the LIN_* set first, then its own
 enum ConBuf {
   CON_W2 = LIN_NBUF,  // W2 = U^T V_A = Kn^-1 K_s A^T, Np x Rp
   CON_H,              // H = A Sigma A^T + diag(s^2), Rp x Rp, identity padding
@@ -1700,7 +1684,7 @@ enum ConBuf {
   CON_OUT,            // (mu' | sd'), Mp each
   CON_NBUF
 };
-static_assert(CON_NBUF <= 32, "gpf_ctx::n_buf");
+static_assert(CON_NBUF <= KeptSet::NMAX && PDRAW_NBUF <= KeptSet::NMAX, "KeptSet holds up to NMAX buffers");
 
 struct ConPlan {
   LinPlan lin;  // (its LIN_PART also holds the partial tiles of this call's own products)
@@ -1727,7 +1711,7 @@ static ConPlan con_plan(const gpf_ctx* c, int64_t M, int R, int64_t Cc) {
   q.bytes[CON_BS] = 2 * Rp * 8;
   q.bytes[CON_VSQ] = q.bytes[CON_VZ] = (size_t)p.nt * C * 8;
   q.bytes[CON_OUT] = 2 * Mp * 8;
-  for (int i = 0; i < CON_NBUF; ++i) q.total += (double)q.bytes[i];
+  q.total = device_bytes(q.bytes, 0, CON_NBUF);
   return q;
 }
 
@@ -1740,9 +1724,7 @@ int gpf_predict_conditioned(gpf_ctx* c, const double* ls, const double* xfit, in
   if (M < 0 || R < 0 || chunk < 0) return bad_arg(c, "gpf_predict_conditioned: M, R and chunk must be >= 0");
   if (!ls) return bad_arg(c, "gpf_predict_conditioned: null length scales");
   if (M > 0 && R > 0 && (!xfit || !w || !b || !sv || !mu_out || !sd_out)) return bad_arg(c, "gpf_predict_conditioned: null buffer");
-  for (int k = 0; k < c->d; ++k)
-    if (!(ls[k] > 0.0) || !std::isfinite(ls[k]))
-      return bad_arg(c, "gpf_predict_conditioned: length scales must be finite and > 0");
+  if (int rl = check_ls(c, "gpf_predict_conditioned", ls, (size_t)c->d)) return rl;
   if (M > (int64_t)1 << 30) return bad_arg(c, "gpf_predict_conditioned: M > 2^30");
   if (R > 1024) return bad_arg(c, "gpf_predict_conditioned: R > 1024 (larger R is not built yet)");
   if (M == 0 || R == 0) return GPF_OK;
@@ -1760,41 +1742,30 @@ int gpf_predict_conditioned(gpf_ctx* c, const double* ls, const double* xfit, in
   if (int rw = ensure_work(c, 1, knobs)) return rw;
   int64_t Cc = std::min<int64_t>(chunk > 0 ? chunk : 16384, 65536);  // (as gpf_predict_linear)
   Cc = ((Cc + T - 1) / T) * T;
+  KeptSet& ks = c->kept[KEPT_CON];
   ConPlan q = con_plan(c, M, R, Cc);
-  bool fits = true;
-  for (int i = 0; i < CON_NBUF; ++i) fits = fits && q.bytes[i] <= c->n_cap[i];
-  if (!fits) {
-    GPF_HIP(c, hipStreamSynchronize(c->stream));
-    free_pcon(c);
-    size_t fr = 0, tot = 0;
-    GPF_HIP(c, hipMemGetInfo(&fr, &tot));
-    const double budget = 0.5 * (double)fr;
-    while (q.total > budget && q.lin.Cc > T) {  // fewer query points per pass
+  if (!ks.fits(q.bytes, CON_NBUF)) {
+    Budget bg;
+    if (int rb = half_free(c, &ks, &bg)) return rb;
+    while (q.total > bg.half && q.lin.Cc > T) {  // fewer query points per pass
       Cc = std::max<int64_t>(T, ((q.lin.Cc / 2 + T - 1) / T) * T);
       q = con_plan(c, M, R, Cc);
     }
-    if (q.total > budget) {
-      int64_t fit = 0;  // the largest multiple of the tile that fits at this R (the bytes grow with M)
-      for (int64_t lo = 0, hi = q.lin.Mp / T; lo < hi;) {
-        const int64_t mid = (lo + hi + 1) / 2;
-        if (con_plan(c, mid * T, R, T).total <= budget) fit = mid * T, lo = mid; else hi = mid - 1;
-      }
+    if (q.total > bg.half) {
+      const int64_t fit = largest_tiled(q.lin.Mp, [&](int64_t m) { return con_plan(c, m, R, T).total <= bg.half; });
       c->err = "gpf_predict_conditioned: the weights, the coordinates and the operands for M=" + std::to_string(M) + ", R=" +
                std::to_string(R) + " at N=" + std::to_string(c->N) + " need " + std::to_string((long long)(q.total / 1048576.0)) +
-               " MiB at 128 query points per pass, more than half of the free " + std::to_string((long long)(fr / 1048576)) +
+               " MiB at 128 query points per pass, more than half of the free " + std::to_string((long long)(bg.fr / 1048576)) +
                " MiB of device memory; the largest M that fits at this R is " + std::to_string(fit);
       return GPF_BAD_ARG;
     }
-    for (int i = 0; i < CON_NBUF; ++i) {
-      GPF_HIP(c, hipMalloc(&c->n_buf[i], q.bytes[i]));
-      c->n_cap[i] = q.bytes[i];
-    }
+    if (int rg = ks.regrow(c, q.bytes, 0, CON_NBUF)) return rg;
   }
   const LinPlan& p = q.lin;
   Cc = p.Cc;
   const int64_t Np = p.Np, Mp = p.Mp;
   const int Rp = p.Rp, Rt = p.Rt, nt = p.nt, d = p.d;
-  auto buf = [&](int i) { return (double*)c->n_buf[i]; };
+  auto buf = [&](int i) { return ks.as(i); };
   double *G = buf(LIN_G), *xf = buf(LIN_XF), *blk = buf(LIN_BLK), *V = buf(LIN_V), *S = buf(LIN_COV), *amu = buf(LIN_MU);
   double *pt = buf(LIN_PART), *W2 = buf(CON_W2), *H = buf(CON_H), *Lh = buf(CON_LH), *strip = buf(CON_STRIP), *Xt = buf(CON_XT);
   double *Cq = buf(CON_C), *E = buf(CON_E), *dv = buf(CON_G), *g = dv + Rp, *dchi = dv + 2 * Rp, *bs = buf(CON_BS);
@@ -1802,7 +1773,7 @@ int gpf_predict_conditioned(gpf_ctx* c, const double* ls, const double* xfit, in
   hipStream_t st = c->stream;
 
   // pass 1: gpf_predict_linear's pipeline (B, V_A, G, Q, S = A Sigma A^T and A mu stay on the device)
-  int rc = lin_enqueue(c, knobs, c->n_buf, p, ls, xfit, M, w, R);
+  int rc = lin_enqueue(c, knobs, ks.p, p, ls, xfit, M, w, R);
   // b and s, then H and d = b - A mu, W2 = U^T V_A (U lower triangular: the depth tiles k < i are zeros)
   if (!rc && (hipMemcpyAsync(bs, b, (size_t)R * 8, hipMemcpyHostToDevice, st) != hipSuccess ||
               hipMemcpyAsync(bs + Rp, sv, (size_t)R * 8, hipMemcpyHostToDevice, st) != hipSuccess ||
@@ -1903,9 +1874,7 @@ int gpf_predict_conditioned(gpf_ctx* c, const double* ls, const double* xfit, in
   }
   hipStreamSynchronize(st);
   if (c->prof) harvest(c);
-  double held = 0.0;
-  for (int i = 0; i < CON_NBUF; ++i) held += (double)c->n_cap[i];
-  if (held > keep_bytes(knobs)) free_pcon(c);
+  ks.trim(knobs);
   return rc;
 }
 
@@ -2023,8 +1992,7 @@ int gpf_lml_batch(gpf_ctx* c, const double* ls, int P, double* lml, double* grad
   if (P < 0 || (P > 0 && (!ls || !lml))) return bad_arg(c, "gpf_lml_batch: bad arguments");
   if (c->N <= 0) return bad_arg(c, "gpf_lml_batch: call gpf_set_data first");
   const int d = c->d, nt = c->nt;
-  for (size_t i = 0; i < (size_t)P * d; ++i)
-    if (!(ls[i] > 0.0) || !std::isfinite(ls[i])) return bad_arg(c, "gpf_lml_batch: length scales must be finite and > 0");
+  if (int rl = check_ls(c, "gpf_lml_batch", ls, (size_t)P * d)) return rl;
   if (P == 0) return GPF_OK;
   hipSetDevice(c->device);
   const int64_t N = c->N, Np = c->Npad;
@@ -2100,10 +2068,34 @@ static double pbatch_col_bytes(const gpf_ctx* c) { return 8.0 * ((double)c->Npad
 // ... and of the call whatever the chunks: the coordinates, the mixture state, (mix_mu | mix_sd), the weights
 static double pbatch_fixed_bytes(const gpf_ctx* c, int64_t Mp, int P) { return 8.0 * ((c->d + 6.0) * (double)Mp + P); }
 
-static double pbatch_held(const gpf_ctx* c) {
-  double b = 0.0;
-  for (const Scratch* s : {&c->b_xf, &c->b_ks, &c->b_vsq, &c->b_vz, &c->b_w, &c->b_state, &c->b_mix, &c->b_each}) b += (double)s->cap;
-  return b;
+// gpf_predict_batch's kept buffers
+enum PbatchBuf {
+  PBATCH_XF = 0,  // the query coordinates, d x Mp
+  PBATCH_KS,      // the chunk's K_s blocks, pc x Np x Cq
+  PBATCH_VSQ,     // the vsq / vz partials, pc x nt x Cq each
+  PBATCH_VZ,
+  PBATCH_W,       // the weights, P
+  PBATCH_STATE,   // the mixture state, 4 x Mp
+  PBATCH_MIX,     // (mix_mu | mix_sd), 2 x Mp
+  PBATCH_EACH,    // (mu_p | sd_p | var_p) of the pass, pc x Cq each
+  PBATCH_HEACH,   // pinned host copy of (mu_p | sd_p), when the caller asks for per-particle output
+  PBATCH_NBUF
+};
+constexpr unsigned PBATCH_PINNED = 1u << PBATCH_HEACH;
+
+// npc: particles per chunk x padded query columns per pass, as pbatch_plan sized them (on
+// pbatch_col_bytes / pbatch_fixed_bytes: the same bytes per column and per call)
+static SetPlan pbatch_bytes(const gpf_ctx* c, int64_t Mp, int P, size_t npc, bool each) {
+  SetPlan p{};
+  p.bytes[PBATCH_XF] = (size_t)c->d * Mp * 8;
+  p.bytes[PBATCH_KS] = npc * (size_t)c->Npad * 8;
+  p.bytes[PBATCH_VSQ] = p.bytes[PBATCH_VZ] = npc * c->nt * 8;
+  p.bytes[PBATCH_W] = (size_t)P * 8;
+  p.bytes[PBATCH_STATE] = (size_t)4 * Mp * 8;
+  p.bytes[PBATCH_MIX] = (size_t)2 * Mp * 8;
+  p.bytes[PBATCH_EACH] = 3 * npc * 8;
+  p.bytes[PBATCH_HEACH] = each ? 2 * npc * 8 : 0;
+  return p;
 }
 
 // The particle-chunk capacity pc and the query chunk cq (padded columns per pass) of a
@@ -2162,11 +2154,11 @@ static int pbatch_plan(gpf_ctx* c, const Knobs& k, int P, int64_t M, int64_t chu
   const double per = (double)bytes_per_particle(c), col = pbatch_col_bytes(c), fixed = pbatch_fixed_bytes(c, Mp, P);
   int pc = std::min(P, 65535);  // (the particle is a grid axis of k_predict_vsq_batch)
   if (k.max_chunk.set) pc = (int)std::max<long long>(1, std::min<long long>(pc, k.max_chunk.i));
-  if (pbatch_plan_pure((double)fr, pbatch_held(c), c->cap, per, col, fixed, pc, cq0, chunk == 0 ? keep_bytes(k) : 0.0,
+  if (pbatch_plan_pure((double)fr, c->kept[KEPT_PBATCH].held(), c->cap, per, col, fixed, pc, cq0, chunk == 0 ? keep_bytes(k) : 0.0,
                        k.mem_fraction.set ? k.mem_fraction.f : 0.85, plan))
     return GPF_OK;
   const double mfit = (0.5 * plan->left - col * T) / (8.0 * (c->d + 6.0));
-  const double all = (double)fr + pbatch_held(c) + (double)c->cap * per;
+  const double all = (double)fr + c->kept[KEPT_PBATCH].held() + (double)c->cap * per;
   c->err = "gpf_predict_batch: N=" + std::to_string(c->N) + ", M=" + std::to_string(M) +
            " do not fit half of the free device memory with one particle at chunk 128: " +
            (mfit >= 1.0 ? "the largest M that fits at this N is about " + std::to_string((long long)mfit)
@@ -2185,8 +2177,7 @@ int gpf_predict_batch(gpf_ctx* c, const double* ls, int P, const double* w, cons
   if (P > 0 && M > 0 && (!ls || !xfit || !mix_mu || !mix_sd)) return bad_arg(c, "gpf_predict_batch: null buffer");
   const int d = c->d, nt = c->nt;
   if (ls)
-    for (size_t i = 0; i < (size_t)P * d; ++i)
-      if (!(ls[i] > 0.0) || !std::isfinite(ls[i])) return bad_arg(c, "gpf_predict_batch: length scales must be finite and > 0");
+    if (int rl = check_ls(c, "gpf_predict_batch", ls, (size_t)P * d)) return rl;
   // the weights, normalised to sum 1 (null: equal)
   std::vector<double> wn((size_t)P, P > 0 ? 1.0 / (double)P : 0.0);
   if (w && P > 0) {
@@ -2217,26 +2208,14 @@ int gpf_predict_batch(gpf_ctx* c, const double* ls, int P, const double* w, cons
   if ((rc = ensure_work(c, cap, knobs))) return rc;
   cap = std::min(cap, c->cap);
   const size_t npc = (size_t)cap * (size_t)Cq;
-  if ((rc = c->b_xf.grow(c, (size_t)d * Mp * 8, false, true))) return rc;
-  if ((rc = c->b_ks.grow(c, npc * Np * 8, false, true))) return rc;
-  if ((rc = c->b_vsq.grow(c, npc * nt * 8, false, true))) return rc;
-  if ((rc = c->b_vz.grow(c, npc * nt * 8, false, true))) return rc;
-  if ((rc = c->b_w.grow(c, (size_t)P * 8, false, true))) return rc;
-  if ((rc = c->b_state.grow(c, (size_t)4 * Mp * 8, false, true))) return rc;
-  if ((rc = c->b_mix.grow(c, (size_t)2 * Mp * 8, false, true))) return rc;
-  if ((rc = c->b_each.grow(c, 3 * npc * 8, false, true))) return rc;  // (mu_p | sd_p | var_p), pc x Cq each
-  if (each) {
-    if (c->b_heach_cap < 2 * npc * 8) {
-      hipHostFree(c->b_heach);
-      c->b_heach = nullptr;
-      c->b_heach_cap = 0;
-      GPF_HIP(c, hipHostMalloc((void**)&c->b_heach, 2 * npc * 8, hipHostMallocDefault));
-      c->b_heach_cap = 2 * npc * 8;
-    }
-  }
-  double *d_xf = c->b_xf.as<double>(), *d_ks = c->b_ks.as<double>(), *d_vsq = c->b_vsq.as<double>();
-  double *d_vz = c->b_vz.as<double>(), *d_w = c->b_w.as<double>(), *d_st = c->b_state.as<double>();
-  double *d_mix = c->b_mix.as<double>(), *d_emu = c->b_each.as<double>(), *d_evar = d_emu + 2 * npc;
+  // (the budget check was the plan's: it counted what the set holds as free, and the regrow gives it back first)
+  KeptSet& ks = c->kept[KEPT_PBATCH];
+  const SetPlan need = pbatch_bytes(c, Mp, P, npc, each);
+  if (!ks.fits(need.bytes, PBATCH_NBUF))
+    if ((rc = ks.regrow(c, need.bytes, PBATCH_PINNED, PBATCH_NBUF))) return rc;
+  double *d_xf = ks.as(PBATCH_XF), *d_ks = ks.as(PBATCH_KS), *d_vsq = ks.as(PBATCH_VSQ), *d_vz = ks.as(PBATCH_VZ);
+  double *d_w = ks.as(PBATCH_W), *d_st = ks.as(PBATCH_STATE), *d_mix = ks.as(PBATCH_MIX), *d_emu = ks.as(PBATCH_EACH);
+  double *d_evar = d_emu + 2 * npc, *heach = ks.as(PBATCH_HEACH);
   double* d_esd = each ? d_emu + npc : nullptr;
   // the query coordinates (leading dimension Mp), the weights and the zeroed mixture state, once
   GPF_HIP(c, hipMemcpy2DAsync(d_xf, (size_t)Mp * 8, xfit, (size_t)M * 8, (size_t)M * 8, (size_t)d, hipMemcpyHostToDevice,
@@ -2291,15 +2270,15 @@ int gpf_predict_batch(gpf_ctx* c, const double* ls, int P, const double* w, cons
       });
       if (rc) break;
       if (each) {
-        if (hipMemcpyAsync(c->b_heach, d_emu, 2 * npc * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        if (hipMemcpyAsync(heach, d_emu, 2 * npc * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
             hipStreamSynchronize(c->stream) != hipSuccess) {
           rc = GPF_HIP_ERROR;
           c->err = "gpf_predict_batch: copy back failed";
           break;
         }
         for (int q = 0; q < pc; ++q) {
-          if (mu_PM) std::memcpy(mu_PM + (size_t)(s + q) * M + s0, c->b_heach + (size_t)q * Cq, (size_t)m * 8);
-          if (sd_PM) std::memcpy(sd_PM + (size_t)(s + q) * M + s0, c->b_heach + npc + (size_t)q * Cq, (size_t)m * 8);
+          if (mu_PM) std::memcpy(mu_PM + (size_t)(s + q) * M + s0, heach + (size_t)q * Cq, (size_t)m * 8);
+          if (sd_PM) std::memcpy(sd_PM + (size_t)(s + q) * M + s0, heach + npc + (size_t)q * Cq, (size_t)m * 8);
         }
       }
     }
@@ -2328,7 +2307,7 @@ int gpf_predict_batch(gpf_ctx* c, const double* ls, int P, const double* w, cons
   }
   hipStreamSynchronize(c->stream);
   if (c->prof) harvest(c);
-  if (pbatch_held(c) > keep_bytes(knobs)) free_pbatch(c);
+  ks.trim(knobs);
   return rc;
 }
 
@@ -2481,6 +2460,26 @@ int gpf_mfma_peak(gpf_ctx* c, int blocks, int iters, double* tflops) {
   return GPF_OK;
 }
 
+// gpf_prob_surface's kept row-chunk buffers
+enum PsurfBuf {
+  PSURF_T = 0,  // the tails as given and compacted, rows x E each
+  PSURF_CMP,
+  PSURF_INFO,   // one double4 per row (gpf::k_prob_prep)
+  PSURF_Y,      // the surface, rows x PS_POINTS each
+  PSURF_P,
+  PSURF_OK,     // the row flags
+  PSURF_NBUF
+};
+
+static SetPlan psurf_plan(int64_t rows, int Ea) {
+  SetPlan p{};
+  p.bytes[PSURF_T] = p.bytes[PSURF_CMP] = (size_t)rows * Ea * 8;
+  p.bytes[PSURF_INFO] = (size_t)rows * sizeof(double4);
+  p.bytes[PSURF_Y] = p.bytes[PSURF_P] = (size_t)rows * gpf::PS_POINTS * 8;
+  p.bytes[PSURF_OK] = (size_t)rows * 4;
+  return p;
+}
+
 // Probability surface (calc_prob_surf.py:15-30,67-81) of M rows of E tail entries each.
 int gpf_prob_surface(gpf_ctx* c, const double* tails, int64_t M, int E, double* y, double* p, int* ok) {
   if (!c) return GPF_BAD_ARG;
@@ -2490,20 +2489,14 @@ int gpf_prob_surface(gpf_ctx* c, const double* tails, int64_t M, int E, double* 
   hipSetDevice(c->device);
   const int64_t chunk = std::min<int64_t>(M, 1 << 20);
   const int Ea = std::max(E, 1);
-  if (c->s_rows < chunk || c->s_e < Ea) {  // grow-only (rows and tail width)
-    GPF_HIP(c, hipStreamSynchronize(c->stream));
-    free_psurf(c);
-    GPF_HIP(c, hipMalloc(&c->s_t, (size_t)chunk * Ea * 8));
-    GPF_HIP(c, hipMalloc(&c->s_cmp, (size_t)chunk * Ea * 8));
-    GPF_HIP(c, hipMalloc(&c->s_info, (size_t)chunk * sizeof(double4)));
-    GPF_HIP(c, hipMalloc(&c->s_y, (size_t)chunk * gpf::PS_POINTS * 8));
-    GPF_HIP(c, hipMalloc(&c->s_p, (size_t)chunk * gpf::PS_POINTS * 8));
-    GPF_HIP(c, hipMalloc(&c->s_ok, (size_t)chunk * 4));
-    c->s_rows = chunk;
-    c->s_e = Ea;
-  }
-  double *dt = c->s_t, *dy = c->s_y, *dp = c->s_p;
-  int* dok = c->s_ok;
+  // (no budget check: a chunk is at most 2^20 rows)
+  KeptSet& ks = c->kept[KEPT_PSURF];
+  const SetPlan need = psurf_plan(chunk, Ea);
+  if (!ks.fits(need.bytes, PSURF_NBUF))
+    if (int rg = ks.regrow(c, need.bytes, 0, PSURF_NBUF)) return rg;
+  double *dt = ks.as(PSURF_T), *dcmp = ks.as(PSURF_CMP), *dy = ks.as(PSURF_Y), *dp = ks.as(PSURF_P);
+  double4* dinfo = ks.as<double4>(PSURF_INFO);
+  int* dok = ks.as<int>(PSURF_OK);
   int rc = GPF_OK;
   for (int64_t s = 0; s < M && rc == GPF_OK; s += chunk) {
     const int64_t m = std::min<int64_t>(chunk, M - s);
@@ -2514,9 +2507,9 @@ int gpf_prob_surface(gpf_ctx* c, const double* tails, int64_t M, int E, double* 
     // algorithmic bytes: the tails read, y and p written, the row flags
     const double bytes = (double)m * (E * 8.0 + 2.0 * gpf::PS_POINTS * 8.0 + 4.0);
     rc = launch(c, PC_PSURF, bytes, [&] {
-      hipLaunchKernelGGL(gpf::k_prob_prep, dim3(blocks_for(m)), dim3(NTHR), 0, c->stream, dt, m, E, c->s_cmp, c->s_info);
-      hipLaunchKernelGGL(gpf::k_prob_surf, dim3(blocks_for(m * gpf::PS_POINTS)), dim3(NTHR), 0, c->stream, c->s_cmp,
-                         c->s_info, m, E, dy, dp, dok);
+      hipLaunchKernelGGL(gpf::k_prob_prep, dim3(blocks_for(m)), dim3(NTHR), 0, c->stream, dt, m, E, dcmp, dinfo);
+      hipLaunchKernelGGL(gpf::k_prob_surf, dim3(blocks_for(m * gpf::PS_POINTS)), dim3(NTHR), 0, c->stream, dcmp, dinfo, m, E,
+                         dy, dp, dok);
     });
     if (rc) break;
     if (hipMemcpyAsync(y + s * gpf::PS_POINTS, dy, (size_t)m * gpf::PS_POINTS * 8, hipMemcpyDeviceToHost, c->stream) !=
@@ -2531,7 +2524,7 @@ int gpf_prob_surface(gpf_ctx* c, const double* tails, int64_t M, int E, double* 
   }
   if (rc == GPF_HIP_ERROR && c->err.empty()) c->err = "gpf_prob_surface: HIP error";
   hipStreamSynchronize(c->stream);
-  if ((double)c->s_rows * (2.0 * c->s_e + 2.0 * gpf::PS_POINTS + 4.5) * 8.0 > keep_bytes(Knobs::from_env())) free_psurf(c);
+  ks.trim(Knobs::from_env());
   return rc;
 }
 
