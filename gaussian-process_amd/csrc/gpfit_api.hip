@@ -725,6 +725,26 @@ int gpf_set_grid(gpf_ctx* c, const double* sig, const double* expct, int K, cons
   if (!c) return GPF_BAD_ARG;
   if (c->d <= 0) return bad_arg(c, "gpf_set_grid: call gpf_set_data first");
   if (K < 2 || K > gpf::KGRID_MAX || !sig || !expct || !lo || !hi) return bad_arg(c, "gpf_set_grid: bad grid");
+  // k_points bisects |pull_k| <= 1 over k, which is the reference's K comparisons only on a finite,
+  // non-decreasing grid (the reference computes something for any order: a deliberate deviation).
+  // Checked before the context or the device is touched, so a rejected grid leaves the old one whole.
+  for (int k = 0; k < K; ++k) {
+    char m[128];
+    if (!std::isfinite(sig[k])) {
+      std::snprintf(m, sizeof m, "gpf_set_grid: sigma_vals[%d] is not finite", k);
+      return bad_arg(c, m);
+    }
+    if (k > 0 && sig[k] < sig[k - 1]) {
+      std::snprintf(m, sizeof m, "gpf_set_grid: sigma_vals must be non-decreasing, sigma_vals[%d] < sigma_vals[%d]", k, k - 1);
+      return bad_arg(c, m);
+    }
+  }
+  for (int k = 0; k < K; ++k)
+    if (!std::isfinite(expct[k])) {
+      char m[128];
+      std::snprintf(m, sizeof m, "gpf_set_grid: expected[%d] is not finite", k);
+      return bad_arg(c, m);
+    }
   hipSetDevice(c->device);
   GPF_HIP(c, hipStreamSynchronize(c->stream));
   if (K != c->K) {

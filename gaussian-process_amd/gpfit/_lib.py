@@ -252,6 +252,14 @@ class Context:
     def set_grid(self, sigma_vals, expected, lo, hi):
         s, ex = _f64(sigma_vals), _f64(expected)
         lo, hi = _f64(lo).reshape(-1), _f64(hi).reshape(-1)
+        # gpf_set_grid reads K doubles of each grid array and d of each bound: check the lengths here
+        if s.ndim != 1:
+            raise ValueError(f"set_grid: sigma_vals must be one-dimensional, got shape {s.shape}")
+        if ex.shape != s.shape:
+            raise ValueError(f"set_grid: expected has shape {ex.shape}, sigma_vals {s.shape}")
+        if not lo.shape == hi.shape == (self.d,):
+            raise ValueError(f"set_grid: lo {lo.shape} and hi {hi.shape} must both be ({self.d},), the data's d "
+                             "(call set_data first)")
         key = _digest(s, ex, lo, hi)
         if key == self._grid_key:
             return

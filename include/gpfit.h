@@ -65,7 +65,14 @@ int gpf_set_data(gpf_ctx* ctx, const double* x_dN, const double* y,
 
 /* Objective grid and search box: sigma_vals/expected are the K-point grid of
  * find_len_scales.py:66-67 (K = 1000 in the reference), lo/hi the (d,) bounds of
- * :56-61. */
+ * :56-61. 2 <= K <= 4096; sigma_vals and expected hold K doubles, lo and hi d.
+ * sigma_vals must be finite and non-decreasing (equal neighbours are allowed)
+ * and expected finite: otherwise GPF_BAD_ARG, gpf_last_error names the first
+ * offending index, and the grid set before stays in force untouched. This is a
+ * deliberate deviation from the reference, which computes a score for any
+ * order: the device finds each point's first covered multiple by bisection,
+ * which equals the reference's K comparisons only on a sorted grid. Sort the
+ * grid (and expected with it) before the call. */
 int gpf_set_grid(gpf_ctx* ctx, const double* sigma_vals, const double* expected,
                  int K, const double* lo, const double* hi);
 
