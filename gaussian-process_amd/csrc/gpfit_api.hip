@@ -707,6 +707,10 @@ int gpf_set_data(gpf_ctx* c, const double* x, const double* y, const double* e, 
   free_work(c);
   hipFree(c->d_x); hipFree(c->d_y); hipFree(c->d_e);
   c->d_x = c->d_y = c->d_e = nullptr;
+  if (d != c->d) {  // the search box is per dimension: a new d discards it (gpf_eval_batch asks for a new gpf_set_grid)
+    c->h_lo.clear();
+    c->h_hi.clear();
+  }
   c->N = N;
   c->d = d;
   c->nt = (int)((N + T - 1) / T);
@@ -747,7 +751,7 @@ int gpf_set_grid(gpf_ctx* c, const double* sig, const double* expct, int K, cons
     }
   hipSetDevice(c->device);
   GPF_HIP(c, hipStreamSynchronize(c->stream));
-  if (K != c->K) {
+  if (K != c->K || !c->d_sig) {  // (no d_sig: K is the placeholder of a call that needs no grid)
     free_work(c);  // histogram size depends on K
     hipFree(c->d_sig); hipFree(c->d_exp);
     c->d_sig = c->d_exp = nullptr;
@@ -773,6 +777,11 @@ int gpf_eval_batch(gpf_ctx* c, const double* ls, int P, double* loss, double* mu
   if (bad_idx) *bad_idx = -1;
   if (P < 0 || (P > 0 && (!ls || !loss))) return bad_arg(c, "gpf_eval_batch: bad arguments");
   if (c->N <= 0 || c->K <= 0) return bad_arg(c, "gpf_eval_batch: call gpf_set_data and gpf_set_grid first");
+  // the box is read per dimension below (h_lo[k], k < d) and on the device (k_score): it must be the one of
+  // this d. It is missing after a gpf_set_data that changed d, and when only gpf_log_marginal_likelihood or
+  // gpf_debug_factor gave K a value
+  if ((int)c->h_lo.size() != c->d || (int)c->h_hi.size() != c->d || !c->d_sig)
+    return bad_arg(c, "gpf_eval_batch: no grid for this dimension: call gpf_set_grid after gpf_set_data");
   hipSetDevice(c->device);
   const Knobs knobs = Knobs::from_env();
   const int d = c->d;

@@ -267,10 +267,21 @@ class Context:
                     "gpf_set_grid")
         self._grid_key = key
 
+    # gpf_eval_batch, gpf_predict, gpf_log_marginal_likelihood and gpf_debug_factor read d doubles per
+    # length-scale row (and d rows of x_fit) whatever the caller's arrays hold: the shapes are checked here
+    def _check_positions(self, P):
+        if P.ndim != 2 or (self.d and P.shape[1] != self.d):
+            raise ValueError(f"positions must be (P, {self.d})")
+
+    def _check_lengths(self, ls):
+        if self.d and ls.shape[0] != self.d:
+            raise ValueError(f"lengths must be ({self.d},)")
+
     def eval_batch(self, positions, want_mu_sd=False):
         P = _f64(positions)
         if P.ndim == 1:
             P = P.reshape(1, -1)
+        self._check_positions(P)
         n = P.shape[0]
         loss = np.empty(n)
         mu = np.empty((n, self.N)) if want_mu_sd else None
@@ -289,6 +300,7 @@ class Context:
         P = _f64(positions)
         if P.ndim == 1:
             P = P.reshape(1, -1)
+        self._check_positions(P)
         loss = np.empty(P.shape[0])
         bad = ctypes.c_int(-1)
         rc = self.lib.gpf_eval_batch_sharded(self._h, comm.handle, _ptr(P), P.shape[0], _ptr(loss), ctypes.byref(bad))
@@ -302,6 +314,10 @@ class Context:
     def predict(self, lengths, x_fit, batch_size=10000):
         ls = _f64(lengths).reshape(-1)
         xf = _f64(x_fit)
+        if xf.ndim != 2:
+            raise ValueError("x_fit must be (d, M)")
+        if self.d and (xf.shape[0] != self.d or ls.shape[0] != self.d):
+            raise ValueError(f"x_fit must be ({self.d}, M) and lengths ({self.d},)")
         m = xf.shape[1]
         mu, sd = np.empty(m), np.empty(m)
         self._check(self.lib.gpf_predict(self._h, _ptr(ls), _ptr(xf), m, int(batch_size), _ptr(mu), _ptr(sd)),
@@ -450,6 +466,11 @@ class Context:
     def kernel(self, x1, x2, l):
         a, b = _f64(x1), _f64(x2)
         ls = _f64(l).reshape(-1)
+        # gpf_kernel reads d rows of both point sets and d length scales, d = x1's
+        if a.ndim != 2 or b.ndim != 2 or b.shape[0] != a.shape[0]:
+            raise ValueError("x1 must be (d, N1) and x2 (d, N2)")
+        if ls.shape[0] != a.shape[0]:
+            raise ValueError(f"l must be ({a.shape[0]},)")
         out = np.empty((a.shape[1], b.shape[1]))
         self._check(self.lib.gpf_kernel(self._h, _ptr(a), a.shape[1], _ptr(b), b.shape[1], a.shape[0],
                                         _ptr(ls), _ptr(out)), "gpf_kernel")
@@ -457,6 +478,7 @@ class Context:
 
     def log_marginal_likelihood(self, lengths):
         ls = _f64(lengths).reshape(-1)
+        self._check_lengths(ls)
         out = ctypes.c_double(0.0)
         self._check(self.lib.gpf_log_marginal_likelihood(self._h, _ptr(ls), ctypes.byref(out)),
                     "gpf_log_marginal_likelihood")
@@ -542,6 +564,7 @@ class Context:
     def debug_factor(self, lengths):
         """(L, U, z, alpha) of one particle: Npad x Npad factor and inverse (diagnostic)."""
         ls = _f64(lengths).reshape(-1)
+        self._check_lengths(ls)
         t = self.lib.gpf_tile()
         npad = -(-self.N // t) * t
         L, U = np.empty((npad, npad)), np.empty((npad, npad))
@@ -578,13 +601,18 @@ class Context:
     def kmeans_set(self, X):
         """Keep the (n, d) centred points on the device for kmeans_step (gpf_kmeans_set)."""
         X = np.ascontiguousarray(X, dtype=np.float64)
+        if X.ndim != 2:
+            raise ValueError("X must be (n, d)")
         self._check(self.lib.gpf_kmeans_set(self._h, _ptr(X), X.shape[0], X.shape[1]), "gpf_kmeans_set")
-        self._km_n = X.shape[0]
+        self._km_n, self._km_d = X.shape
 
     def kmeans_step(self, centers, update=True, want_dist=False):
         """One Lloyd E-step (+ M-step sums) against centers (k, d) (gpf_kmeans_step):
         (labels, sums, counts, dist or None)."""
         C = np.ascontiguousarray(centers, dtype=np.float64)
+        # gpf_kmeans_step reads k x d doubles with the d of kmeans_set
+        if C.ndim != 2 or C.shape[1] != self._km_d:
+            raise ValueError(f"centers must be (k, {self._km_d})")
         k, d = C.shape
         labels = np.empty(self._km_n, dtype=np.int32)
         sums = np.empty((k, d)) if update else None

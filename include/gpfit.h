@@ -59,7 +59,13 @@ const char* gpf_last_error(gpf_ctx* ctx);
 
 /* Training data: x_dN is (d, N) dims-major; y, e are (N,).
  * Reference: the (x_known, y_known, e_known) tuple members pickled per task at
- * find_len_scales.py:76,102,133; here uploaded once per len_scale_opt call. */
+ * find_len_scales.py:76,102,133; here uploaded once per len_scale_opt call.
+ * 1 <= d <= 32 and 1 <= N <= 2^20, else GPF_BAD_ARG and the data set before stays.
+ * Every later call reads d doubles per length-scale row and d rows of query
+ * coordinates: the caller's buffers must have this d (the library cannot see
+ * their size; the Python binding checks the shapes). A call that changes d
+ * discards the search box of gpf_set_grid, which is per dimension: gpf_eval_batch
+ * then returns GPF_BAD_ARG until gpf_set_grid has been called again. */
 int gpf_set_data(gpf_ctx* ctx, const double* x_dN, const double* y,
                  const double* e, int64_t N, int d);
 
@@ -82,7 +88,10 @@ int gpf_set_grid(gpf_ctx* ctx, const double* sigma_vals, const double* expected,
  * GPU. mu_PN / sd_PN (nullable, (P, N) row-major) receive the GP mean / sd at
  * the training points (GP_func.py:36-40 with x_fit = x_known); rows of
  * sentinel particles are filled with NaN. On GPF_NOT_PD *bad_idx is the first
- * particle whose covariance is not positive definite. */
+ * particle whose covariance is not positive definite. GPF_BAD_ARG, before
+ * anything is read or written: no data, no grid, or no gpf_set_grid since the
+ * gpf_set_data that gave the data its present d (the box would be indexed past
+ * its end, or hold the bounds of other dimensions). */
 int gpf_eval_batch(gpf_ctx* ctx, const double* ls_Pd, int P, double* loss_P,
                    double* mu_PN, double* sd_PN, int* bad_idx);
 

@@ -227,12 +227,12 @@ def test_pso_on_gpu_end_to_end(ctx, f4, k, capsys):
 
 
 @pytest.mark.parametrize("n,d,k,dup", [(1024, 3, 100, 0), (4096, 3, 100, 0), (16384, 4, 100, 0), (600, 2, 100, 400),
-                                       (3000, 5, 37, 0)])
+                                       (3000, 5, 37, 0), (3000, 7, 37, 0), (2000, 32, 50, 0)])
 def test_kmeans_fit_on_gpu_matches_sklearn(ctx, n, d, k, dup):
     """The KMeans subsample's fit with the Lloyd E/M-steps on the GPU (gpf_kmeans_step,
     gpfit.kmeans): labels equal to sklearn's KMeans(k, n_init='auto', random_state=0).fit (the
     reference's call, find_len_scales.py:27-31), centres within 1e-12; duplicate points (empty
-    clusters relocated) included."""
+    clusters relocated) included; d = 7 and 32 run k_km_assign's run-time-d path."""
     from sklearn.cluster import KMeans
     from gpfit.kmeans import kmeans_fit
     rng = np.random.default_rng(n + d + k + dup)
@@ -248,9 +248,12 @@ def test_kmeans_fit_on_gpu_matches_sklearn(ctx, n, d, k, dup):
 
 def test_kmeans_step_buffers_follow_k_and_d(ctx):
     """gpf_kmeans_step keeps its centre buffers between calls: a call with more dimensions at the
-    same or a smaller k, or more clusters, must resize them (a d-only change once overran them)."""
+    same or a smaller k, or more clusters, must resize them (a d-only change once overran them). The
+    sequence goes on through d = 7, 9 and 32 (k_km_assign's run-time-d path; 6 and 8 are templated), d
+    rising and falling on the live context."""
     rng = np.random.default_rng(5)
-    for n, d, k in ((500, 2, 50), (700, 5, 50), (400, 3, 120), (300, 4, 10)):
+    for n, d, k in ((500, 2, 50), (700, 5, 50), (400, 3, 120), (300, 4, 10), (400, 32, 100), (600, 6, 40),
+                    (500, 9, 64), (600, 7, 40), (500, 8, 64)):
         X = rng.uniform(size=(n, d))
         C = X[rng.choice(n, k, replace=False)]
         ctx.kmeans_set(X)

@@ -185,11 +185,13 @@ def test_both_dispatch_orders_give_the_same_bits(ctx, monkeypatch):
         assert np.max(np.abs(info["sd"][p] ** 2 - var_ref)) < TOL
 
 
-@pytest.mark.parametrize("d", [1, 2, 3, 5])
+@pytest.mark.parametrize("d", [1, 2, 3, 5, 9, 32])
 def test_cross_cov_batch_is_bitwise_cross_cov(ctx, monkeypatch, d):
     """k_cross_cov_batch (a copy of k_cross_cov's body with the particle on a grid axis) against k_cross_cov
     itself, launched once per particle (GPF_PREDBATCH_KS=0, an internal switch kept for this test): every
-    instantiation — d = 1, 2, 3 templated, d = 5 the run-time one — with three particles, so that the
+    instantiation — d = 1, 2, 3 templated, d = 5, 9 and 32 the run-time one (at 32 with 76,032 bytes of
+    dynamic LDS; tests/test_dimension_gpu.py repeats 9 and 32 with length scales that keep K_s of order 1,
+    which these do not) — with three particles, so that the
     offsets of particles 1 and 2 are pinned too; and at P = 1 bitwise predict(), which uses k_cross_cov."""
     N, M = 257, 300
     x, y, e, ls, q = _case(N, d, M)
