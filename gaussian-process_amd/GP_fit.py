@@ -8,7 +8,7 @@ messages follow GP_fit.py:20-164.
 Optional options.yaml keys (absent = reference behaviour): pso_num_particles (40),
 pso_max_iter (500), pso_max_points (100), pso_seed (none: unseeded global RNG);
 len_scale_objective ("calibration": the reference's swarm; "marginal_likelihood": the
-maximum-marginal-likelihood fit, which reuses pso_max_points and pso_seed),
+maximum-marginal-likelihood fit; "loo": the leave-one-out fit; both reuse pso_max_points and pso_seed),
 mle_num_starts (40) and hyper_samples (K >= 1: the written mean and sd are marginalised over K
 length-scale samples, gpfit.hyper.predict_marginal, instead of taken at the one fitted vector; it
 reuses pso_max_points and pso_seed).

@@ -13,7 +13,7 @@ import numpy as np
 
 from gpfit._lib import default_context
 
-__all__ = ["GP", "GP_cov", "GP_draws", "kernel_func"]
+__all__ = ["GP", "GP_cov", "GP_draws", "GP_loo", "kernel_func"]
 
 
 def GP(x_known, y_known, e_known, x_fit, lengths, batch_size=10000):
@@ -88,6 +88,15 @@ def GP_draws(x_known, y_known, e_known, x_fit, lengths, n_draws, seed=None, meth
     (gpf_posterior_draws). The normals are default_rng(seed)'s on both paths."""
     from gpfit.posterior import sample_posterior
     return sample_posterior(x_known, y_known, e_known, x_fit, lengths, n_draws, seed=seed, method=method)[0]
+
+
+def GP_loo(x_known, y_known, e_known, lengths):
+    """Leave-one-out check of the fit: (mu (N,), sd (N,)), every measured y_i predicted from the other
+    N - 1 points, sd the predictive sd of the measurement (e_i^2 included), so (y - mu) / sd is N(0, 1)
+    if the error bars are honest (gpf_loo_batch; gpfit.loo.loo_predict also returns the pulls, their
+    coverage and the LOO log predictive density)."""
+    from gpfit.loo import loo_predict
+    return loo_predict(x_known, y_known, e_known, lengths)[:2]
 
 
 def kernel_func(x1, x2, l):

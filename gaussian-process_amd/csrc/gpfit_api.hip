@@ -31,6 +31,7 @@
 #include "gpf_densechol.hip"
 #include "gpf_conditioned.hip"
 #include "gpf_lmlgrad.hip"
+#include "gpf_loo.hip"
 #include "gpf_probsurf.hip"
 #include "gpf_hull.hip"
 #include "gpf_kmeans.hip"
@@ -188,6 +189,10 @@ struct gpf_ctx {
   // grow-only and outside the chunk workspace (bytes_per_particle): the evaluation path's chunk
   // capacity does not depend on it
   Scratch gpart;
+  // gpf_loo_batch: the chunk's per-particle vectors [particles][LV_N][Npad] and, with the gradient, the
+  // dense B = diag(sqrt g) W [particles][Npad][Npad] behind them. Outside the chunk workspace like
+  // gpart, but given back with it (free_work), so a regrown workspace is sized on all the free memory
+  Scratch loo;
   // pinned host staging for the per-batch transfers (async DMA, capturable in graphs)
   double* h_ls = nullptr;
   double* h_loss = nullptr;
@@ -322,7 +327,7 @@ static void free_work(gpf_ctx* c) {
   c->d_cflag = nullptr;
   hipFree(c->d_pst);
   c->d_pst = nullptr;
-  for (Scratch* s : {&c->part, &c->cnt, &c->la, &c->pb, &c->pstart, &c->lb}) s->release();
+  for (Scratch* s : {&c->part, &c->cnt, &c->la, &c->pb, &c->pstart, &c->lb, &c->loo}) s->release();
   c->d_L = c->d_U = c->d_yb = c->d_s2p = c->d_szp = c->d_ls = c->d_mu = c->d_sd = c->d_loss = nullptr;
   c->d_info = nullptr;
   c->d_hist = nullptr;
@@ -2084,6 +2089,118 @@ int gpf_lml_batch(gpf_ctx* c, const double* ls, int P, double* lml, double* grad
       lml[p] = bad ? -INFINITY : c->h_loss[q];
       if (grad)
         for (int k = 0; k < d; ++k) grad[(size_t)p * d + k] = bad ? NAN : hg[(size_t)q * d + k];
+    }
+  }
+  return ret;
+}
+
+// ---- gpf_loo_batch: leave-one-out predictions, their log predictive density and its gradient ----
+int gpf_loo_batch(gpf_ctx* c, const double* ls, int P, double* lpd, double* grad, double* mu, double* sd, int* status,
+                  int* bad_idx) {
+  if (!c) return GPF_BAD_ARG;
+  if (bad_idx) *bad_idx = -1;
+  if (P < 0 || (P > 0 && (!ls || !lpd))) return bad_arg(c, "gpf_loo_batch: bad arguments");
+  if (c->N <= 0) return bad_arg(c, "gpf_loo_batch: call gpf_set_data first");
+  const int d = c->d, nt = c->nt;
+  if (int rl = check_ls(c, "gpf_loo_batch", ls, (size_t)P * d)) return rl;
+  if (P == 0) return GPF_OK;
+  hipSetDevice(c->device);
+  const int64_t N = c->N, Np = c->Npad;
+  const Knobs knobs = Knobs::from_env();
+  int rc = ensure_work(c, P, knobs);
+  if (rc) return rc;
+  const int ntile = nt * (nt + 1) / 2;
+  // particles per pass: the workspace's capacity, lowered to what the call's own buffer (the vectors
+  // and, with the gradient, B) fits in the memory that is free beside the workspace
+  const size_t per = ((size_t)gpf::LV_N * Np + (grad ? (size_t)Np * Np : 0)) * 8;
+  int pcm = std::min(c->cap, P);
+  if ((size_t)pcm * per > c->loo.cap) {
+    size_t fr = 0, tot = 0;
+    GPF_HIP(c, hipStreamSynchronize(c->stream));
+    GPF_HIP(c, hipMemGetInfo(&fr, &tot));
+    const double frac = knobs.mem_fraction.set ? knobs.mem_fraction.f : 0.85;
+    const long long fit = (long long)(((double)fr + (double)c->loo.cap) * frac / (double)per);
+    if (fit < 1) {
+      c->err = "gpf_loo_batch: not enough device memory for one particle at N=" + std::to_string(c->N);
+      return GPF_HIP_ERROR;
+    }
+    pcm = (int)std::min<long long>(pcm, fit);
+  }
+  if ((rc = c->loo.grow(c, (size_t)pcm * per, false, true))) return rc;
+  double* d_vec = c->loo.as<double>();
+  double* d_B = d_vec + (size_t)pcm * gpf::LV_N * Np;
+  double* d_grad = nullptr;
+  std::vector<double> hg;
+  if (grad) {
+    // (synchronised regrow: the previous call's gradient pass may still be reading it)
+    if ((rc = c->gpart.grow(c, ((size_t)pcm * ntile * d + (size_t)pcm * d) * 8, false, true))) return rc;
+    d_grad = c->gpart.as<double>() + (size_t)pcm * ntile * d;
+    hg.resize((size_t)pcm * d);
+  }
+  const size_t vpitch = (size_t)gpf::LV_N * Np * 8;
+  int ret = GPF_OK;
+  for (int s = 0; s < P; s += pcm) {
+    const int pc = std::min(pcm, P - s);
+    std::memcpy(c->h_ls, ls + (size_t)s * d, (size_t)pc * d * 8);
+    GPF_HIP(c, hipMemcpyAsync(c->d_ls, c->h_ls, (size_t)pc * d * 8, hipMemcpyHostToDevice, c->stream));
+    rc = run_factor(c, pc, knobs);
+    if (rc) return rc;
+    // the per-point quantities into the call's vectors, the density into the loss slots of the workspace
+    rc = launch(c, PC_LOSS, 0.0, [&] {
+      hipLaunchKernelGGL(gpf::k_loo_points, dim3(pc), dim3(NTHR), 0, c->stream, (int)N, (int)Np, nt, c->d_y, c->d_s2p, c->d_szp,
+                         d_vec, c->d_loss);
+    });
+    if (rc) return rc;
+    if (grad) {
+      // W = U^T U: k_lml_grad's flops, the sum over the lower tiles (I, J) of 2 T^3 (nt - I)
+      double fl = 0.0;
+      for (int I = 0; I < nt; ++I) fl += 2.0 * (double)T * T * T * (double)(nt - I) * (I + 1);
+      rc = launch(c, PC_LOSS, fl * pc, [&] {
+        hipLaunchKernelGGL(gpf::k_loo_w, dim3((unsigned)ntile, pc), dim3(gpf::Geo<T>::NTH), 0, c->stream, (int)Np, nt, c->d_U, d_B);
+      });
+      if (rc) return rc;
+      const int nmb = (int)(Np / gpf::MIR_B);
+      rc = launch(c, PC_LOSS, 0.0, [&] {
+        hipLaunchKernelGGL(gpf::k_loo_scale_mirror, dim3((unsigned)(nmb * (nmb + 1) / 2), pc), dim3(NTHR), 0, c->stream, (int)N,
+                           (int)Np, d_B, d_vec);
+        hipLaunchKernelGGL(gpf::k_loo_u, dim3((unsigned)nmb, pc), dim3(NTHR), 0, c->stream, (int)N, (int)Np, d_B, d_vec);
+      });
+      if (rc) return rc;
+      // G = B^T B reduced against the kernel derivative: every lower tile over the full depth, 2 T^3 nt
+      rc = launch(c, PC_LOSS, 2.0 * (double)T * T * T * nt * (double)ntile * pc, [&] {
+        hipLaunchKernelGGL(gpf::k_loo_grad, dim3((unsigned)ntile, pc), dim3(gpf::Geo<T>::NTH), 0, c->stream, (int)N, (int)Np, nt,
+                           d, c->d_x, c->d_ls, d_B, d_vec, c->gpart.as<double>());
+        hipLaunchKernelGGL(gpf::k_lml_grad_sum, dim3(pc), dim3(gpf::DMAX), 0, c->stream, ntile, d, c->gpart.as<double>(), c->d_ls,
+                           d_grad);
+      });
+      if (rc) return rc;
+      GPF_HIP(c, hipMemcpyAsync(hg.data(), d_grad, (size_t)pc * d * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (mu)
+      GPF_HIP(c, hipMemcpy2DAsync(mu + (size_t)s * N, (size_t)N * 8, d_vec + (size_t)gpf::LV_MU * Np, vpitch, (size_t)N * 8,
+                                  (size_t)pc, hipMemcpyDeviceToHost, c->stream));
+    if (sd)
+      GPF_HIP(c, hipMemcpy2DAsync(sd + (size_t)s * N, (size_t)N * 8, d_vec + (size_t)gpf::LV_SD * Np, vpitch, (size_t)N * 8,
+                                  (size_t)pc, hipMemcpyDeviceToHost, c->stream));
+    GPF_HIP(c, hipMemcpyAsync(c->h_loss, c->d_loss, (size_t)pc * 8, hipMemcpyDeviceToHost, c->stream));
+    GPF_HIP(c, hipMemcpyAsync(c->h_info, c->d_info, (size_t)pc * 4, hipMemcpyDeviceToHost, c->stream));
+    GPF_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->prof) harvest(c);
+    for (int q = 0; q < pc; ++q) {
+      const int p = s + q;
+      const int st = particle_status(c, q);
+      if (st == GPF_HIP_ERROR) return st;
+      const bool bad = st != GPF_OK;
+      if (bad && ret == GPF_OK) {
+        ret = GPF_NOT_PD;
+        if (bad_idx) *bad_idx = p;
+      }
+      if (status) status[p] = bad ? GPF_NOT_PD : GPF_OK;
+      lpd[p] = bad ? -INFINITY : c->h_loss[q];
+      if (grad)
+        for (int k = 0; k < d; ++k) grad[(size_t)p * d + k] = bad ? NAN : hg[(size_t)q * d + k];
+      if (bad && mu) std::fill(mu + (size_t)p * N, mu + (size_t)(p + 1) * N, (double)NAN);
+      if (bad && sd) std::fill(sd + (size_t)p * N, sd + (size_t)(p + 1) * N, (double)NAN);
     }
   }
   return ret;

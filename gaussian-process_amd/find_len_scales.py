@@ -16,8 +16,9 @@ init_positions, seed.
 
 objective="marginal_likelihood" replaces the swarm by a maximum-marginal-likelihood
 fit (gpfit.mle.fit_lml: batched starts, then L-BFGS-B with the gradient from
-gpf_lml_batch); it takes num_starts, max_points and seed. The default,
-objective="calibration", is the reference's search.
+gpf_lml_batch); objective="loo" maximises the leave-one-out log predictive density
+instead (gpfit.loo.fit_loo, gradient from gpf_loo_batch). Both take num_starts,
+max_points and seed. The default, objective="calibration", is the reference's search.
 """
 import numpy as np
 
@@ -31,15 +32,22 @@ __all__ = ["len_scale_opt", "wass_loss", "evaluate_loss", "evaluate_loss_helper"
 def len_scale_opt(x_known, y_known, e_known, PSO_progress, *, num_particles=40, max_iter=500,
                   max_points=100, init_positions=None, seed=None, objective="calibration", num_starts=40):
     """PSO search for the per-dimension length scales (find_len_scales.py:22-150), or with
-    objective="marginal_likelihood" the maximum-marginal-likelihood fit (gpfit.mle.fit_lml)."""
+    objective="marginal_likelihood" the maximum-marginal-likelihood fit (gpfit.mle.fit_lml), with
+    objective="loo" the leave-one-out fit (gpfit.loo.fit_loo)."""
     if objective == "marginal_likelihood":
         from gpfit.mle import fit_lml
         best, _ = fit_lml(np.asarray(x_known, dtype=np.float64), np.asarray(y_known, dtype=np.float64),
                           np.asarray(e_known, dtype=np.float64), num_starts=num_starts, max_points=max_points,
                           seed=seed, verbose=bool(PSO_progress))
         return best
+    if objective == "loo":
+        from gpfit.loo import fit_loo
+        best, _ = fit_loo(np.asarray(x_known, dtype=np.float64), np.asarray(y_known, dtype=np.float64),
+                          np.asarray(e_known, dtype=np.float64), num_starts=num_starts, max_points=max_points,
+                          seed=seed, verbose=bool(PSO_progress))
+        return best
     if objective != "calibration":
-        raise ValueError(f"len_scale_opt: unknown objective {objective!r} (calibration or marginal_likelihood)")
+        raise ValueError(f"len_scale_opt: unknown objective {objective!r} (calibration, marginal_likelihood or loo)")
     best, _ = particle_swarm(np.asarray(x_known, dtype=np.float64), np.asarray(y_known, dtype=np.float64),
                              np.asarray(e_known, dtype=np.float64), PSO_progress,
                              num_particles=num_particles, max_iter=max_iter, max_points=max_points,

@@ -46,6 +46,7 @@ SIGNATURES = {
     "gpf_kernel": (ctypes.c_int, [_vp, _dp, ctypes.c_int64, _dp, ctypes.c_int64, ctypes.c_int, _dp, _dp]),
     "gpf_log_marginal_likelihood": (ctypes.c_int, [_vp, _dp, _dp]),
     "gpf_lml_batch": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _dp, _dp, _ip, _ip]),
+    "gpf_loo_batch": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _dp, _dp, _dp, _dp, _ip, _ip]),
     "gpf_predict_batch": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _dp, _dp, ctypes.c_int64, ctypes.c_int64,
                                          _dp, _dp, _dp, _dp, _ip]),
     "gpf_predict_batch_plan": (ctypes.c_int, [ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_double,
@@ -505,6 +506,33 @@ class Context:
         if rc != GPF_NOT_PD or strict:
             self._check(rc, "gpf_lml_batch", bad)
         return lml, g
+
+    def loo_batch(self, positions, grad=True, points=False, strict=True):
+        """Leave-one-out log predictive density of every row of positions (P, d) and, with grad, its
+        gradient in the length scales (gpf_loo_batch): (lpd (P,), grad (P, d) or None), and with
+        points also (mu (P, N), sd (P, N)), every training point's prediction from the other N - 1
+        (the sd of the measured value: e_i^2 included). Needs set_data only. A particle whose
+        covariance is not positive definite raises LinAlgError with .particle set to its row
+        (strict), or gets lpd = -inf and NaN gradient, mu and sd rows while the other rows are
+        computed (strict=False)."""
+        P = _f64(positions)
+        if P.ndim == 1:
+            P = P.reshape(1, -1)
+        n = P.shape[0]
+        if self.d and P.shape[1] != self.d:
+            raise ValueError(f"positions must be (P, {self.d})")
+        lpd = np.empty(n)
+        g = np.empty((n, P.shape[1])) if grad else None
+        mu = np.empty((n, self.N)) if points else None
+        sd = np.empty((n, self.N)) if points else None
+        status = np.zeros(n, dtype=np.int32)
+        bad = ctypes.c_int(-1)
+        rc = self.lib.gpf_loo_batch(self._h, _ptr(P), n, _ptr(lpd), _ptr(g) if grad else None,
+                                    _ptr(mu) if points else None, _ptr(sd) if points else None,
+                                    status.ctypes.data_as(_ip), ctypes.byref(bad))
+        if rc != GPF_NOT_PD or strict:
+            self._check(rc, "gpf_loo_batch", bad)
+        return (lpd, g, mu, sd) if points else (lpd, g)
 
     def predict_batch(self, positions, x_fit, weights=None, chunk=0, want_each=False):
         """predict() at every row of positions (P, d) in one batched call, and the mixture of the P

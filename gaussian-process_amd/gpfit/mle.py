@@ -57,17 +57,11 @@ def _call(value_and_grad, positions, grad):
     return lml, (g if grad else None)
 
 
-def fit_lml(x, y, e, *, num_starts=NUM_STARTS, num_polish=NUM_POLISH, max_points=MAX_POINTS, seed=None,
-            value_and_grad=None, ctx=None, verbose=True):
-    """Length scales that maximise the log marginal likelihood: (best_l (d,), info).
-
-    ``value_and_grad(positions (P, d)) -> (lml (P,), grad (P, d))`` injects an evaluator (the CPU
-    tests); the default is gpf_lml_batch on this process's GPU. A point whose covariance is not
-    positive definite (lml = -inf or NaN) is a losing point, never an error. Under WORLD_SIZE > 1
-    every rank runs the same seeded fit redundantly. info: "lml" (at best_l), "evals" (value
-    evaluations), "grad_evals", "box" (lower, upper), "starts" (positions, lml) and "polished" (one
-    dict per polished start: start, x, lml, start_lml, nfev, nit, message).
-    """
+def fit_gradient(x, y, e, *, who, key, done_msg, value_label, device_evaluator, num_starts, num_polish, max_points,
+                 seed, value_and_grad, ctx, verbose):
+    """The two-stage driver behind fit_lml and gpfit.loo.fit_loo: maximises the value an evaluator
+    returns with its gradient in the length scales. ``who`` names the caller in messages, ``key`` the
+    value in info ("lml", "lpd"), ``device_evaluator(ctx)`` builds the default evaluator."""
     from scipy.optimize import minimize
 
     x = np.asarray(x, dtype=np.float64)
@@ -80,12 +74,12 @@ def fit_lml(x, y, e, *, num_starts=NUM_STARTS, num_polish=NUM_POLISH, max_points
                                           ctx=None if injected else ctx)
     lower = np.maximum(lower, LOWER_FRACTION * upper)
     if not np.all(upper > lower):
-        raise ValueError("fit_lml: the search box is empty (a coordinate has no spread)")
+        raise ValueError(f"{who}: the search box is empty (a coordinate has no spread)")
     if injected:
         comm = default_comm()
     else:
         ctx.set_data(x, y, e)
-        value_and_grad = _device_evaluator(ctx)
+        value_and_grad = device_evaluator(ctx)
         comm = default_comm(ctx)
     seed = share_seed(seed, comm)
     d = x.shape[0]
@@ -118,15 +112,32 @@ def fit_lml(x, y, e, *, num_starts=NUM_STARTS, num_polish=NUM_POLISH, max_points
         val = -float(res.fun) if res.fun < BAD_VALUE else -np.inf
         if not val >= start_lml[s]:  # (a line search that only met losing points: keep the start)
             ls, val = starts[s].copy(), float(start_lml[s])
-        polished.append({"start": starts[s].copy(), "x": ls, "lml": val, "start_lml": float(start_lml[s]),
+        polished.append({"start": starts[s].copy(), "x": ls, key: val, "start_" + key: float(start_lml[s]),
                          "nfev": int(res.nfev), "nit": int(res.nit), "message": str(res.message)})
-    best = max(polished, key=lambda r: r["lml"])
+    best = max(polished, key=lambda r: r[key])
     if verbose:
-        print("Marginal-likelihood fit completed.")
+        print(done_msg)
         print("Optimal length scale found:")
         print(best["x"])
-        print("Log marginal likelihood:")
-        print(best["lml"])
-    info = {"lml": best["lml"], "evals": counts["evals"], "grad_evals": counts["grad_evals"],
+        print(value_label)
+        print(best[key])
+    info = {key: best[key], "evals": counts["evals"], "grad_evals": counts["grad_evals"],
             "box": (lower, upper), "starts": (starts, start_lml), "polished": polished}
     return best["x"].copy(), info
+
+
+def fit_lml(x, y, e, *, num_starts=NUM_STARTS, num_polish=NUM_POLISH, max_points=MAX_POINTS, seed=None,
+            value_and_grad=None, ctx=None, verbose=True):
+    """Length scales that maximise the log marginal likelihood: (best_l (d,), info).
+
+    ``value_and_grad(positions (P, d)) -> (lml (P,), grad (P, d))`` injects an evaluator (the CPU
+    tests); the default is gpf_lml_batch on this process's GPU. A point whose covariance is not
+    positive definite (lml = -inf or NaN) is a losing point, never an error. Under WORLD_SIZE > 1
+    every rank runs the same seeded fit redundantly. info: "lml" (at best_l), "evals" (value
+    evaluations), "grad_evals", "box" (lower, upper), "starts" (positions, lml) and "polished" (one
+    dict per polished start: start, x, lml, start_lml, nfev, nit, message).
+    """
+    return fit_gradient(x, y, e, who="fit_lml", key="lml", done_msg="Marginal-likelihood fit completed.",
+                        value_label="Log marginal likelihood:", device_evaluator=_device_evaluator,
+                        num_starts=num_starts, num_polish=num_polish, max_points=max_points, seed=seed,
+                        value_and_grad=value_and_grad, ctx=ctx, verbose=verbose)

@@ -248,6 +248,34 @@ int gpf_log_marginal_likelihood(gpf_ctx* ctx, const double* ls, double* out);
 int gpf_lml_batch(gpf_ctx* ctx, const double* ls_Pd, int P, double* lml_P, double* grad_Pd,
                   int* status_P, int* bad_idx);
 
+/* Batched leave-one-out (LOO) cross-validation and the gradient of its log predictive density in the
+ * length scales (same model as gpf_lml_batch; Rasmussen & Williams 5.4.2), the validation report and
+ * the objective of gpfit.loo.fit_loo. ls_Pd is (P, d) row-major. Needs gpf_set_data only.
+ * With W = Kn^-1, alpha = W y, w_i = W_ii:
+ *   mu_PN[p,i]   = y_i - alpha_i / w_i: the prediction of the measured y_i from the other N - 1 points
+ *                  (nullable)
+ *   sd_PN[p,i]   = sqrt(1 / w_i): its predictive sd, e_i^2 included, not clipped (nullable)
+ *   lpd_P[p]     = sum_i [1/2 log w_i - 1/2 alpha_i^2 / w_i] - N/2 log(2 pi)
+ *   grad_Pd[p,k] = dlpd/dl_k = sum_{i>j} (u_i alpha_j + u_j alpha_i - 2 G_ij) K_ij (x_ik - x_jk)^2 / l_k^3,
+ *                  c_i = alpha_i / w_i, g_i = 1/2 (1 + alpha_i^2 / w_i) / w_i, u = W c, G = W diag(g) W,
+ *                  K the noise-free kernel (nullable: without it neither O(N^3) pass is run)
+ *   status_P[p]  = GPF_OK or GPF_NOT_PD (nullable)
+ * The pull (y_i - mu_i) / sd_i = alpha_i / sqrt(w_i) is N(0, 1) under the model.
+ * Everything is computed on the device from the factorisation's U = L^-1 and its partial sums of
+ * diag(W) and alpha; the particles are chunked as in gpf_eval_batch, and with the gradient the chunk
+ * is lowered to what a buffer of Npad^2 doubles per particle (B = diag(sqrt g) W) fits beside the
+ * workspace. A particle whose covariance is not positive definite gets lpd = -inf and NaN gradient,
+ * mu and sd rows and does not spoil the others: every other output is written, then the call
+ * returns GPF_NOT_PD with *bad_idx the first such particle.
+ * GPF_BAD_ARG, before any device work, for a null ctx, no data set, P < 0, a null ls_Pd or lpd_P with
+ * P > 0, or any length scale that is not finite and > 0. P == 0 returns GPF_OK.
+ * Repeating a call on the same context and data gives the same bits (fixed-order sums, no
+ * floating-point atomics), and lpd, mu and sd do not depend on whether the gradient is asked for;
+ * results may differ in the last bits between batch sizes, as the factorisation's schedule depends
+ * on the batch. The call keeps its own buffers: it changes no bit of any other call. */
+int gpf_loo_batch(gpf_ctx* ctx, const double* ls_Pd, int P, double* lpd_P, double* grad_Pd,
+                  double* mu_PN, double* sd_PN, int* status_P, int* bad_idx);
+
 /* gpf_predict for P length-scale samples at once, and their mixture: the length scales are not known
  * exactly (the fit ends with many nearly-as-good candidates), so the prediction is taken at P samples
  * ls_Pd (P, d) row-major with the weights w_P (nullable: equal; else >= 0, normalised to sum 1 here)
@@ -398,6 +426,9 @@ int gpf_set_profiling(gpf_ctx* ctx, int on);
  *  [3] diag kernel ms    [4] diag launches   [5] diag algorithmic flops
  *  [6] K-build ms        [7] K-build launches[8] K-build algorithmic bytes
  *  [9] loss kernel ms    [10] loss launches  [11] evals (non-sentinel)
+ *       (gpf_lml_batch: its value kernels, one entry, and k_lml_grad with k_lml_grad_sum, one entry;
+ *       gpf_loo_batch: k_loo_points; k_loo_w (flops ~ P N^3 / 3); k_loo_scale_mirror with k_loo_u;
+ *       k_loo_grad (flops P ntile 2 T^3 nt) with k_lml_grad_sum — one entry each)
  *  [12] factorisation wall ms (K build + diag + steps of all particle groups, which run
  *       on concurrent streams, so [0]/[3]/[6] may overlap)  [13] calls  [14] its flops
  *  [15] prediction V = U K_s kernel ms  [16] launches  [17] algorithmic flops
