@@ -8,7 +8,10 @@ messages follow GP_fit.py:20-164.
 Optional options.yaml keys (absent = reference behaviour): pso_num_particles (40),
 pso_max_iter (500), pso_max_points (100), pso_seed (none: unseeded global RNG);
 len_scale_objective ("calibration": the reference's swarm; "marginal_likelihood": the
-maximum-marginal-likelihood fit; "loo": the leave-one-out fit; both reuse pso_max_points and pso_seed),
+maximum-marginal-likelihood fit; "loo": the leave-one-out fit; both reuse pso_max_points and pso_seed;
+"marginal_likelihood_full": the marginal-likelihood fit of the length scales, a prior amplitude and a
+factor on the quoted errors, gpfit.amplitude.fit_hyper, and the prediction with them, GP_hyper; it
+reuses pso_max_points, pso_seed and mle_num_starts and does not combine with hyper_samples),
 mle_num_starts (40) and hyper_samples (K >= 1: the written mean and sd are marginalised over K
 length-scale samples, gpfit.hyper.predict_marginal, instead of taken at the one fitted vector; it
 reuses pso_max_points and pso_seed).
@@ -21,7 +24,7 @@ import yaml
 
 from convex_hull import fill_convex_hull
 from find_len_scales import len_scale_opt
-from GP_func import GP
+from GP_func import GP, GP_hyper
 from read_in import read_yaml
 
 __all__ = ["process_experiment", "write_individual_file", "write_grouped_file", "write_combined_file",
@@ -67,6 +70,16 @@ def _marginal(x_known, y_known, e_known, x_fit, ls, k, pso):
     return mu, sd
 
 
+def _fit_full(x_known, y_known, e_known, progress, pso):
+    """theta = (l.., a, s) of len_scale_objective: marginal_likelihood_full (gpfit.amplitude.fit_hyper)."""
+    import numpy as np
+    from gpfit.amplitude import fit_hyper
+    kw = {key: pso[key] for key in ("num_starts", "max_points", "seed") if key in pso}
+    theta, _ = fit_hyper(np.asarray(x_known, dtype=np.float64), np.asarray(y_known, dtype=np.float64),
+                         np.asarray(e_known, dtype=np.float64), verbose=bool(progress), **kw)
+    return theta
+
+
 def _merge(frames, on):
     return reduce(lambda a, b: pd.merge(a, b, on=on, how="outer"), frames).fillna(float("inf"))
 
@@ -78,9 +91,18 @@ def process_experiment(x_known, y_known, e_known, resolution, dim_labels, filena
     if x_known.shape[1] == 0:
         print("  Skipping experiment: no valid data points")
         return None
-    ls = len_scale_opt(x_known, y_known, e_known, PSO_progress, **pso)
+    full = pso.get("objective") == "marginal_likelihood_full"
+    if full:
+        if hyper_samples is not None:
+            raise ValueError("options.yaml: hyper_samples does not combine with len_scale_objective: "
+                             "marginal_likelihood_full")
+        ls = _fit_full(x_known, y_known, e_known, PSO_progress, pso)
+    else:
+        ls = len_scale_opt(x_known, y_known, e_known, PSO_progress, **pso)
     grid = fill_convex_hull(x_known.T, resolution)
-    if hyper_samples is None:
+    if full:
+        mu, sd = GP_hyper(x_known, y_known, e_known, grid.T, ls)
+    elif hyper_samples is None:
         mu, sd = GP(x_known, y_known, e_known, grid.T, ls)
     else:
         mu, sd = _marginal(x_known, y_known, e_known, grid.T, ls, hyper_samples, pso)

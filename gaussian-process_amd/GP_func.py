@@ -13,7 +13,7 @@ import numpy as np
 
 from gpfit._lib import default_context
 
-__all__ = ["GP", "GP_cov", "GP_draws", "GP_loo", "kernel_func"]
+__all__ = ["GP", "GP_cov", "GP_draws", "GP_hyper", "GP_loo", "kernel_func"]
 
 
 def GP(x_known, y_known, e_known, x_fit, lengths, batch_size=10000):
@@ -97,6 +97,18 @@ def GP_loo(x_known, y_known, e_known, lengths):
     coverage and the LOO log predictive density)."""
     from gpfit.loo import loo_predict
     return loo_predict(x_known, y_known, e_known, lengths)[:2]
+
+
+def GP_hyper(x_known, y_known, e_known, x_fit, theta):
+    """GP() under a prior amplitude and a noise scale: theta = (l_1 .. l_d, a, s),
+    Kn = a^2 K(l) + s^2 diag(e^2); (mu, sigma) at x_fit (d, M). It is a times GP() on (y / a, e s / a)
+    (gpfit.amplitude.predict_hyper; theta from gpfit.amplitude.fit_hyper)."""
+    from gpfit.amplitude import predict_hyper
+    x_known = np.asarray(x_known, dtype=np.float64)
+    x_fit = np.asarray(x_fit, dtype=np.float64)
+    if x_fit.ndim != 2 or x_fit.shape[0] != x_known.shape[0]:
+        raise ValueError("x_fit must be (d, M) with the same d as x_known")
+    return predict_hyper(x_known, y_known, e_known, x_fit, theta)
 
 
 def kernel_func(x1, x2, l):

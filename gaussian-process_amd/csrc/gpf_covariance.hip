@@ -19,6 +19,8 @@ constexpr int BT = 64;  // covariance build tile
 // Op order mirrors kernel_func (GP_func.py:56-65): a = x / l, |a|^2 summed over
 // dims in order, (|a_i|^2 + |a_j|^2) - 2 a_i.a_j, clamp >= 0, exp(-0.5 r2).
 // Also seeds the per-particle RHS workspace with y (padded with zeros).
+// nfac (nullable): one noise factor r per particle, K = SE + r diag(e^2) (gpf_lml_hyper_batch's
+// r = (s / a)^2), added as (e_i r) e_i: null and r = 1.0 give the same bits, those of e_i e_i.
 // grid: (nb*(nb+1)/2, P) for every lower 64x64 tile, or (3*nt, P) with diag_only: the lower
 // tiles of the 128-wide diagonal blocks only (k_step computes the others itself).
 // ----------------------------------------------------------------------------
@@ -27,7 +29,8 @@ __global__ __launch_bounds__(NTHR) void k_build_cov(int N, int Npad, int d, cons
                                                     const double* __restrict__ ls, double* __restrict__ Lb,
                                                     double* __restrict__ yb, int* __restrict__ info, int diag_only,
                                                     int* __restrict__ dflag, int* __restrict__ cflag,
-                                                    int* __restrict__ pst, long long pstride, int pnt) {
+                                                    int* __restrict__ pst, long long pstride, int pnt,
+                                                    const double* __restrict__ nfac) {
   __shared__ double ai[DMAX][BT];
   __shared__ double aj[DMAX][BT];
   __shared__ double ni[BT], nj[BT];
@@ -47,6 +50,7 @@ __global__ __launch_bounds__(NTHR) void k_build_cov(int N, int Npad, int d, cons
     bj = idx - bi * (bi + 1) / 2;
   }
   const double* lp = ls + (size_t)p * d;
+  const double nf = nfac ? nfac[p] : 1.0;
   if (idx == 0 && tid == 0) {
     info[p] = 0;  // the factorisation kernels only ever set it
     dflag[p] = -1;  // no diagonal block published yet (early diagonal factor, k_step)
@@ -92,7 +96,7 @@ __global__ __launch_bounds__(NTHR) void k_build_cov(int N, int Npad, int d, cons
       double r2 = (ni[r] + nj[c]) - 2.0 * dot;
       r2 = r2 > 0.0 ? r2 : 0.0;  // np.maximum(sq_dist, 0)
       v = exp(-0.5 * r2);
-      if (gi == gj) v = v + e[gi] * e[gi];
+      if (gi == gj) v = v + (e[gi] * nf) * e[gi];
     } else {
       v = (gi == gj) ? 1.0 : 0.0;
     }

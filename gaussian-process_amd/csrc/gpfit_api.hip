@@ -32,6 +32,7 @@
 #include "gpf_conditioned.hip"
 #include "gpf_lmlgrad.hip"
 #include "gpf_loo.hip"
+#include "gpf_hyperlml.hip"
 #include "gpf_probsurf.hip"
 #include "gpf_hull.hip"
 #include "gpf_kmeans.hip"
@@ -175,6 +176,7 @@ struct gpf_ctx {
   double* d_mu = nullptr;
   double* d_sd = nullptr;
   double* d_loss = nullptr;
+  double* d_nfac = nullptr;  // per particle: the noise factor r of K = SE + r diag(e^2) (gpf_lml_hyper_batch)
   int* d_info = nullptr;
   int* d_flag = nullptr;  // per particle: last diagonal block published in the running launch (early_diag)
   int* d_cflag = nullptr;  // per particle: last diagonal block reduced by a SYRK workgroup (defer_syrk); reset by k_build_cov
@@ -193,6 +195,9 @@ struct gpf_ctx {
   // dense B = diag(sqrt g) W [particles][Npad][Npad] behind them. Outside the chunk workspace like
   // gpart, but given back with it (free_work), so a regrown workspace is sized on all the free memory
   Scratch loo;
+  // gpf_lml_hyper_batch: per particle (a, s), the four results of k_hyper_value, alt and alt / a
+  // (Npad doubles each). Its own, like loo: no other call reads or writes it
+  Scratch hyp;
   // pinned host staging for the per-batch transfers (async DMA, capturable in graphs)
   double* h_ls = nullptr;
   double* h_loss = nullptr;
@@ -321,13 +326,15 @@ static void free_work(gpf_ctx* c) {
   hipFree(c->d_L); hipFree(c->d_U); hipFree(c->d_yb); hipFree(c->d_s2p); hipFree(c->d_szp);
   hipFree(c->d_ls); hipFree(c->d_mu); hipFree(c->d_sd); hipFree(c->d_loss); hipFree(c->d_info);
   hipFree(c->d_hist);
+  hipFree(c->d_nfac);
+  c->d_nfac = nullptr;
   hipFree(c->d_flag);
   c->d_flag = nullptr;
   hipFree(c->d_cflag);
   c->d_cflag = nullptr;
   hipFree(c->d_pst);
   c->d_pst = nullptr;
-  for (Scratch* s : {&c->part, &c->cnt, &c->la, &c->pb, &c->pstart, &c->lb, &c->loo}) s->release();
+  for (Scratch* s : {&c->part, &c->cnt, &c->la, &c->pb, &c->pstart, &c->lb, &c->loo, &c->hyp}) s->release();
   c->d_L = c->d_U = c->d_yb = c->d_s2p = c->d_szp = c->d_ls = c->d_mu = c->d_sd = c->d_loss = nullptr;
   c->d_info = nullptr;
   c->d_hist = nullptr;
@@ -336,7 +343,8 @@ static void free_work(gpf_ctx* c) {
 
 static size_t bytes_per_particle(const gpf_ctx* c) {
   const size_t np = (size_t)c->Npad;
-  // (+ the paired block columns' partial slots, nt-1 tiles, allocated when a factorisation pairs)
+  // (+ the paired block columns' partial slots, nt-1 tiles, allocated when a factorisation pairs;
+  // the noise factor's 8 bytes per particle are not counted, so no call's chunking changes)
   return 2 * np * np * 8 + (2 * (size_t)c->nt * np + 3 * np) * 8 + (size_t)(c->K + 1) * 4 + 64 * 8 + 8 +
          (size_t)std::max(c->nt - 1, 0) * T * T * 8;
 }
@@ -366,6 +374,7 @@ static int ensure_work(gpf_ctx* c, int want, const Knobs& k) {
   GPF_HIP(c, hipMalloc(&c->d_mu, (size_t)cap * np * 8));
   GPF_HIP(c, hipMalloc(&c->d_sd, (size_t)cap * np * 8));
   GPF_HIP(c, hipMalloc(&c->d_loss, (size_t)cap * 8));
+  GPF_HIP(c, hipMalloc(&c->d_nfac, (size_t)cap * 8));
   GPF_HIP(c, hipMalloc(&c->d_info, (size_t)cap * 4));
   GPF_HIP(c, hipMalloc(&c->d_flag, (size_t)cap * 4));  // reset by k_build_cov at every factorisation
   GPF_HIP(c, hipMalloc(&c->d_cflag, (size_t)cap * 4));  // likewise
@@ -385,8 +394,8 @@ static int ensure_work(gpf_ctx* c, int want, const Knobs& k) {
 // blocks), then one k_step per 128-wide block column. With the fused diagonal factor (plan.ed false)
 // k_diag factors block 0 first and each launch J factors block J+1 at the end of its critical tile;
 // with the early diagonal factor launch J itself starts with the factor of block J. Joins back
-// into c->stream.
-static int run_factor(gpf_ctx* c, int pc, const Knobs& knobs) {
+// into c->stream. nfac (device, nullable): the particles' noise factors, K = SE + r diag(e^2) (k_build_cov).
+static int run_factor(gpf_ctx* c, int pc, const Knobs& knobs, const double* nfac = nullptr) {
   const int nt = c->nt, Np = (int)c->Npad, N = (int)c->N;
   const double Tf = (double)T, t3 = Tf * Tf * Tf;
   const int nb = Np / BT;
@@ -460,7 +469,7 @@ static int run_factor(gpf_ctx* c, int pc, const Knobs& knobs) {
     int rc = launch_on(c, st, PC_BUILD, 8.0 * nbuild * BT * BT * (double)gc, [&] {
       hipLaunchKernelGGL(gpf::k_build_cov, dim3(nbuild, gc), dim3(NTHR), 0, st, N, Np, c->d, c->d_x, c->d_y, c->d_e,
                          lsg, Lg, yg, ig, (int)(nbuild != ntri), c->d_flag + p0, c->d_cflag + p0,
-                         persist ? c->d_pst : nullptr, (long long)c->cap * nt, nt);
+                         persist ? c->d_pst : nullptr, (long long)c->cap * nt, nt, nfac ? nfac + p0 : nullptr);
     });
     if (rc) return rc;
     if (ed) continue;  // block 0 is factored by launch 0's diagonal workgroups
@@ -2201,6 +2210,110 @@ int gpf_loo_batch(gpf_ctx* c, const double* ls, int P, double* lpd, double* grad
         for (int k = 0; k < d; ++k) grad[(size_t)p * d + k] = bad ? NAN : hg[(size_t)q * d + k];
       if (bad && mu) std::fill(mu + (size_t)p * N, mu + (size_t)(p + 1) * N, (double)NAN);
       if (bad && sd) std::fill(sd + (size_t)p * N, sd + (size_t)(p + 1) * N, (double)NAN);
+    }
+  }
+  return ret;
+}
+
+// ---- gpf_lml_hyper_batch: log marginal likelihood and its gradient in (l, a, s) ----
+int gpf_lml_hyper_batch(gpf_ctx* c, const double* th, int P, double* lml, double* grad, double* qout, int* status,
+                        int* bad_idx) {
+  if (!c) return GPF_BAD_ARG;
+  if (bad_idx) *bad_idx = -1;
+  if (P < 0 || (P > 0 && (!th || !lml))) return bad_arg(c, "gpf_lml_hyper_batch: bad arguments");
+  if (c->N <= 0) return bad_arg(c, "gpf_lml_hyper_batch: call gpf_set_data first");
+  const int d = c->d, nt = c->nt, dh = d + 2;
+  // (a, s) and the noise factor r = (s / a)^2 of every particle: they outlive the chunk loop's copies
+  std::vector<double> has((size_t)P * 2), hr((size_t)P);
+  for (int p = 0; p < P; ++p) {
+    const double* row = th + (size_t)p * dh;
+    if (int rl = check_ls(c, "gpf_lml_hyper_batch", row, (size_t)d)) return rl;
+    const double a = row[d], s = row[d + 1];
+    if (!(a > 0.0) || !std::isfinite(a) || !(s > 0.0) || !std::isfinite(s))
+      return bad_arg(c, "gpf_lml_hyper_batch: amplitude and noise scale must be finite and > 0");
+    const double q = s / a, r = q * q;
+    if (!(r > 0.0) || !std::isfinite(r))
+      return bad_arg(c, "gpf_lml_hyper_batch: the noise factor (s / a)^2 must be finite and > 0");
+    has[(size_t)2 * p] = a;
+    has[(size_t)2 * p + 1] = s;
+    hr[p] = r;
+  }
+  if (P == 0) return GPF_OK;
+  hipSetDevice(c->device);
+  const int64_t N = c->N, Np = c->Npad;
+  const Knobs knobs = Knobs::from_env();
+  int rc = ensure_work(c, P, knobs);
+  if (rc) return rc;
+  const int cap = c->cap, pcm = std::min(cap, P);
+  const int ntile = nt * (nt + 1) / 2;
+  // the call's own vectors: (a, s) | k_hyper_value's results | alt | alt / a
+  // (synchronised regrow: the previous call's kernels may still be reading it)
+  if ((rc = c->hyp.grow(c, ((size_t)pcm * (2 + gpf::HV_N) + 2 * (size_t)pcm * Np) * 8, false, true))) return rc;
+  double* d_as = c->hyp.as<double>();
+  double* d_out = d_as + (size_t)pcm * 2;
+  double* d_al = d_out + (size_t)pcm * gpf::HV_N;
+  double* d_sc = d_al + (size_t)pcm * Np;
+  double* d_grad = nullptr;
+  std::vector<double> hg, ho((size_t)pcm * gpf::HV_N);
+  if (grad) {
+    if ((rc = c->gpart.grow(c, ((size_t)pcm * ntile * d + (size_t)pcm * d) * 8, false, true))) return rc;
+    d_grad = c->gpart.as<double>() + (size_t)pcm * ntile * d;
+    hg.resize((size_t)pcm * d);
+  }
+  int ret = GPF_OK;
+  for (int s = 0; s < P; s += cap) {
+    const int pc = std::min(cap, P - s);
+    for (int q = 0; q < pc; ++q) std::memcpy(c->h_ls + (size_t)q * d, th + (size_t)(s + q) * dh, (size_t)d * 8);
+    GPF_HIP(c, hipMemcpyAsync(c->d_ls, c->h_ls, (size_t)pc * d * 8, hipMemcpyHostToDevice, c->stream));
+    GPF_HIP(c, hipMemcpyAsync(c->d_nfac, hr.data() + s, (size_t)pc * 8, hipMemcpyHostToDevice, c->stream));
+    GPF_HIP(c, hipMemcpyAsync(d_as, has.data() + (size_t)2 * s, (size_t)pc * 2 * 8, hipMemcpyHostToDevice, c->stream));
+    rc = run_factor(c, pc, knobs, c->d_nfac);
+    if (rc) return rc;
+    rc = launch(c, PC_LOSS, 0.0, [&] {
+      hipLaunchKernelGGL(gpf::k_alpha_batch, dim3((unsigned)((N + NTHR - 1) / NTHR), pc), dim3(NTHR), 0, c->stream, (int)N,
+                         (int)Np, nt, c->d_szp, d_al);
+      hipLaunchKernelGGL(gpf::k_hyper_value, dim3(pc), dim3(NTHR), 0, c->stream, (int)N, (int)Np, nt, c->d_y, c->d_e, d_al,
+                         c->d_L, c->d_s2p, d_as, d_out);
+    });
+    if (rc) return rc;
+    if (grad) {
+      // k_lml_grad on alt / a: gpf_lml_batch's flops
+      double fl = 0.0;
+      for (int I = 0; I < nt; ++I) fl += 2.0 * (double)T * T * T * (double)(nt - I) * (I + 1);
+      rc = launch(c, PC_LOSS, fl * pc, [&] {
+        hipLaunchKernelGGL(gpf::k_hyper_scale, dim3((unsigned)((N + NTHR - 1) / NTHR), pc), dim3(NTHR), 0, c->stream, (int)N,
+                           (int)Np, d_al, d_as, d_sc);
+        hipLaunchKernelGGL(gpf::k_lml_grad, dim3((unsigned)ntile, pc), dim3(gpf::Geo<T>::NTH), 0, c->stream, (int)N,
+                           (int)Np, nt, d, c->d_x, c->d_ls, c->d_U, d_sc, c->gpart.as<double>());
+        hipLaunchKernelGGL(gpf::k_lml_grad_sum, dim3(pc), dim3(gpf::DMAX), 0, c->stream, ntile, d, c->gpart.as<double>(), c->d_ls,
+                           d_grad);
+      });
+      if (rc) return rc;
+      GPF_HIP(c, hipMemcpyAsync(hg.data(), d_grad, (size_t)pc * d * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    GPF_HIP(c, hipMemcpyAsync(ho.data(), d_out, (size_t)pc * gpf::HV_N * 8, hipMemcpyDeviceToHost, c->stream));
+    GPF_HIP(c, hipMemcpyAsync(c->h_info, c->d_info, (size_t)pc * 4, hipMemcpyDeviceToHost, c->stream));
+    GPF_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->prof) harvest(c);
+    for (int q = 0; q < pc; ++q) {
+      const int p = s + q;
+      const int st = particle_status(c, q);
+      if (st == GPF_HIP_ERROR) return st;
+      const bool bad = st != GPF_OK;
+      if (bad && ret == GPF_OK) {
+        ret = GPF_NOT_PD;
+        if (bad_idx) *bad_idx = p;
+      }
+      if (status) status[p] = bad ? GPF_NOT_PD : GPF_OK;
+      const double* o = ho.data() + (size_t)q * gpf::HV_N;
+      lml[p] = bad ? -INFINITY : o[gpf::HV_LML];
+      if (qout) qout[p] = bad ? NAN : o[gpf::HV_Q];
+      if (grad) {
+        double* g = grad + (size_t)p * dh;
+        for (int k = 0; k < d; ++k) g[k] = bad ? NAN : hg[(size_t)q * d + k];
+        g[d] = bad ? NAN : o[gpf::HV_DA];
+        g[d + 1] = bad ? NAN : o[gpf::HV_DS];
+      }
     }
   }
   return ret;

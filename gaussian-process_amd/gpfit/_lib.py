@@ -47,6 +47,7 @@ SIGNATURES = {
     "gpf_log_marginal_likelihood": (ctypes.c_int, [_vp, _dp, _dp]),
     "gpf_lml_batch": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _dp, _dp, _ip, _ip]),
     "gpf_loo_batch": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _dp, _dp, _dp, _dp, _ip, _ip]),
+    "gpf_lml_hyper_batch": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _dp, _dp, _dp, _ip, _ip]),
     "gpf_predict_batch": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _dp, _dp, ctypes.c_int64, ctypes.c_int64,
                                          _dp, _dp, _dp, _dp, _ip]),
     "gpf_predict_batch_plan": (ctypes.c_int, [ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_double,
@@ -506,6 +507,33 @@ class Context:
         if rc != GPF_NOT_PD or strict:
             self._check(rc, "gpf_lml_batch", bad)
         return lml, g
+
+    def lml_hyper_batch(self, theta, grad=True, strict=True, want_q=False):
+        """Log marginal likelihood of every row (l_1 .. l_d, a, s) of theta (P, d + 2) under
+        Kn = a^2 K(l) + s^2 diag(e^2) (a: the prior sd, s: a factor on the quoted errors) and, with
+        grad, its gradient in all d + 2 (gpf_lml_hyper_batch): (lml (P,), grad (P, d + 2) or None),
+        and with want_q also Q = y^T Kt^-1 y of the unit-amplitude Kt = K + (s/a)^2 diag(e^2): for
+        fixed l and s/a the best amplitude is sqrt(Q / N). Needs set_data only. A particle whose
+        covariance is not positive definite raises LinAlgError with .particle set to its row
+        (strict), or gets lml = -inf and NaN in its gradient row and Q while the other rows are
+        computed (strict=False)."""
+        th = _f64(theta)
+        if th.ndim == 1:
+            th = th.reshape(1, -1)
+        n = th.shape[0]
+        if th.ndim != 2 or th.shape[1] < 3 or (self.d and th.shape[1] != self.d + 2):
+            raise ValueError(f"theta must be (P, {self.d + 2}): the length scales, then a and s" if self.d
+                             else "theta must be (P, d + 2): the length scales, then a and s")
+        lml = np.empty(n)
+        g = np.empty(th.shape) if grad else None
+        q = np.empty(n) if want_q else None
+        status = np.zeros(n, dtype=np.int32)
+        bad = ctypes.c_int(-1)
+        rc = self.lib.gpf_lml_hyper_batch(self._h, _ptr(th), n, _ptr(lml), _ptr(g) if grad else None,
+                                          _ptr(q) if want_q else None, status.ctypes.data_as(_ip), ctypes.byref(bad))
+        if rc != GPF_NOT_PD or strict:
+            self._check(rc, "gpf_lml_hyper_batch", bad)
+        return (lml, g, q) if want_q else (lml, g)
 
     def loo_batch(self, positions, grad=True, points=False, strict=True):
         """Leave-one-out log predictive density of every row of positions (P, d) and, with grad, its

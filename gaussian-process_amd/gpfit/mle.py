@@ -14,7 +14,8 @@ The data preparation is the swarm's (``gpfit.swarm.prepare``: the KMeans subsamp
 positive gap between coordinates) can be 0, where log l is not defined, so the box used here
 starts at max(lower, 1e-3 * upper).
 
-Model: fixed amplitude 1, fixed noise e^2, ARD squared-exponential, as GP_func.py.
+Model: fixed amplitude 1, fixed noise e^2, ARD squared-exponential, as GP_func.py (gpfit.amplitude
+fits an amplitude and a noise scale as well, with this module's stage 2).
 """
 from __future__ import annotations
 
@@ -57,13 +58,42 @@ def _call(value_and_grad, positions, grad):
     return lml, (g if grad else None)
 
 
+def polish_log(value_and_grad, starts, start_val, order, lower, upper, key, counts):
+    """Stage 2 of the fits: the starts ``order`` polished by L-BFGS-B on minus the evaluator's value in
+    t = log(position) inside the box, d/dlog p_k = p_k d/dp_k. One dict per polished start (start, x,
+    key, start_<key>, nfev, nit, message); counts["evals"] and ["grad_evals"] are advanced."""
+    from scipy.optimize import minimize
+
+    d = starts.shape[1]
+    tlo, thi = np.log(lower), np.log(upper)
+
+    def neg(t):
+        ls = np.exp(t).reshape(1, d)
+        lml, g = _call(value_and_grad, ls, True)
+        counts["evals"] += 1
+        counts["grad_evals"] += 1
+        if not np.isfinite(lml[0]) or not np.all(np.isfinite(g[0])):
+            return BAD_VALUE, np.zeros(d)
+        return -lml[0], -(g[0] * ls[0])
+
+    polished = []
+    for s in order:
+        t0 = np.clip(np.log(starts[s]), tlo, thi)
+        res = minimize(neg, t0, jac=True, method="L-BFGS-B", bounds=list(zip(tlo, thi)))
+        ls = np.clip(np.exp(res.x), lower, upper)
+        val = -float(res.fun) if res.fun < BAD_VALUE else -np.inf
+        if not val >= start_val[s]:  # (a line search that only met losing points: keep the start)
+            ls, val = starts[s].copy(), float(start_val[s])
+        polished.append({"start": starts[s].copy(), "x": ls, key: val, "start_" + key: float(start_val[s]),
+                         "nfev": int(res.nfev), "nit": int(res.nit), "message": str(res.message)})
+    return polished
+
+
 def fit_gradient(x, y, e, *, who, key, done_msg, value_label, device_evaluator, num_starts, num_polish, max_points,
                  seed, value_and_grad, ctx, verbose):
     """The two-stage driver behind fit_lml and gpfit.loo.fit_loo: maximises the value an evaluator
     returns with its gradient in the length scales. ``who`` names the caller in messages, ``key`` the
     value in info ("lml", "lpd"), ``device_evaluator(ctx)`` builds the default evaluator."""
-    from scipy.optimize import minimize
-
     x = np.asarray(x, dtype=np.float64)
     y = np.asarray(y, dtype=np.float64)
     e = np.asarray(e, dtype=np.float64)
@@ -82,7 +112,6 @@ def fit_gradient(x, y, e, *, who, key, done_msg, value_label, device_evaluator, 
         value_and_grad = device_evaluator(ctx)
         comm = default_comm(ctx)
     seed = share_seed(seed, comm)
-    d = x.shape[0]
     counts = {"evals": 0, "grad_evals": 0}
 
     # stage 1: every start in one batched value call
@@ -93,27 +122,7 @@ def fit_gradient(x, y, e, *, who, key, done_msg, value_label, device_evaluator, 
     order = np.argsort(-start_lml, kind="stable")[:max(1, int(num_polish))]
 
     # stage 2: L-BFGS-B on -LML in t = log l
-    tlo, thi = np.log(lower), np.log(upper)
-
-    def neg(t):
-        ls = np.exp(t).reshape(1, d)
-        lml, g = _call(value_and_grad, ls, True)
-        counts["evals"] += 1
-        counts["grad_evals"] += 1
-        if not np.isfinite(lml[0]) or not np.all(np.isfinite(g[0])):
-            return BAD_VALUE, np.zeros(d)
-        return -lml[0], -(g[0] * ls[0])
-
-    polished = []
-    for s in order:
-        t0 = np.clip(np.log(starts[s]), tlo, thi)
-        res = minimize(neg, t0, jac=True, method="L-BFGS-B", bounds=list(zip(tlo, thi)))
-        ls = np.clip(np.exp(res.x), lower, upper)
-        val = -float(res.fun) if res.fun < BAD_VALUE else -np.inf
-        if not val >= start_lml[s]:  # (a line search that only met losing points: keep the start)
-            ls, val = starts[s].copy(), float(start_lml[s])
-        polished.append({"start": starts[s].copy(), "x": ls, key: val, "start_" + key: float(start_lml[s]),
-                         "nfev": int(res.nfev), "nit": int(res.nit), "message": str(res.message)})
+    polished = polish_log(value_and_grad, starts, start_lml, order, lower, upper, key, counts)
     best = max(polished, key=lambda r: r[key])
     if verbose:
         print(done_msg)

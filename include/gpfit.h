@@ -276,6 +276,35 @@ int gpf_lml_batch(gpf_ctx* ctx, const double* ls_Pd, int P, double* lml_P, doubl
 int gpf_loo_batch(gpf_ctx* ctx, const double* ls_Pd, int P, double* lpd_P, double* grad_Pd,
                   double* mu_PN, double* sd_PN, int* status_P, int* bad_idx);
 
+/* Batched log marginal likelihood with a prior amplitude and a noise scale, and its gradient in all
+ * of them: the objective of gpfit.amplitude.fit_hyper. th_Pd2 is (P, d + 2) row-major, each row
+ * (l_1 .. l_d, a, s): a > 0 the prior sd of f, s > 0 a factor on the quoted errors,
+ *   Kn = a^2 K(l) + s^2 diag(e^2) = a^2 Kt,  Kt = K(l) + r diag(e^2),  r = (s / a)^2.
+ * Needs gpf_set_data only. The unit-amplitude Kt is factored by the kernels of every other call (the
+ * K build adds e_i^2 r on the diagonal); with Lt = chol(Kt), Wt = Kt^-1, alt = Wt y, wt_i = Wt_ii,
+ * Q = y^T alt and S = sum_i e_i^2 (alt_i^2 / a^2 - wt_i):
+ *   lml_P[p]         = -Q / (2 a^2) - sum_i log Lt_ii - N log a - N/2 log(2 pi)
+ *   grad_Pd2[p,k<d]  = sum_{i>j} (alt_i alt_j / a^2 - Wt_ij) K_ij (x_ik - x_jk)^2 / l_k^3
+ *   grad_Pd2[p,d]    = dLML/da = (Q / a^2 - N) / a - (s^2 / a^3) S
+ *   grad_Pd2[p,d+1]  = dLML/ds = (s / a^2) S                        (grad_Pd2 nullable: no O(N^3) pass)
+ *   q_P[p]           = Q: for fixed (l, r) the best amplitude is a^2 = Q / N (nullable)
+ *   status_P[p]      = GPF_OK or GPF_NOT_PD (nullable)
+ * At a = s = 1 lml_P and the first d gradient columns are gpf_lml_batch's for the same batch, bit for
+ * bit. The model with (a, s) on (x, y, e) is the unit model on (x, y / a, e s / a) with mu a, sd a and
+ * cov a^2: every other call serves it through that scaling (gpfit.amplitude).
+ * A particle whose Kt is not positive definite gets lml = -inf and NaN in its gradient row and q and
+ * does not spoil the others: every other output is written, then the call returns GPF_NOT_PD with
+ * *bad_idx the first such particle.
+ * GPF_BAD_ARG, before any device work, for a null ctx, no data set, P < 0, a null th_Pd2 or lml_P with
+ * P > 0, any l, a or s that is not finite and > 0, or an (s / a)^2 that is not finite and > 0.
+ * P == 0 returns GPF_OK. Repeating a call gives the same bits (fixed-order sums, no floating-point
+ * atomics), and lml and q do not depend on whether the gradient is asked for. The call keeps its own
+ * buffers: it changes no bit of any other call.
+ * Not built: per-particle (a, s) in gpf_predict_batch and in the length-scale sampler, leave-one-out
+ * with (a, s), a mean function. */
+int gpf_lml_hyper_batch(gpf_ctx* ctx, const double* th_Pd2, int P, double* lml_P, double* grad_Pd2,
+                        double* q_P, int* status_P, int* bad_idx);
+
 /* gpf_predict for P length-scale samples at once, and their mixture: the length scales are not known
  * exactly (the fit ends with many nearly-as-good candidates), so the prediction is taken at P samples
  * ls_Pd (P, d) row-major with the weights w_P (nullable: equal; else >= 0, normalised to sum 1 here)
@@ -428,7 +457,9 @@ int gpf_set_profiling(gpf_ctx* ctx, int on);
  *  [9] loss kernel ms    [10] loss launches  [11] evals (non-sentinel)
  *       (gpf_lml_batch: its value kernels, one entry, and k_lml_grad with k_lml_grad_sum, one entry;
  *       gpf_loo_batch: k_loo_points; k_loo_w (flops ~ P N^3 / 3); k_loo_scale_mirror with k_loo_u;
- *       k_loo_grad (flops P ntile 2 T^3 nt) with k_lml_grad_sum — one entry each)
+ *       k_loo_grad (flops P ntile 2 T^3 nt) with k_lml_grad_sum — one entry each;
+ *       gpf_lml_hyper_batch: as gpf_lml_batch, k_hyper_value among the value kernels and
+ *       k_hyper_scale in the gradient entry)
  *  [12] factorisation wall ms (K build + diag + steps of all particle groups, which run
  *       on concurrent streams, so [0]/[3]/[6] may overlap)  [13] calls  [14] its flops
  *  [15] prediction V = U K_s kernel ms  [16] launches  [17] algorithmic flops
