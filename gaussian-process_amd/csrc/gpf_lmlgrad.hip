@@ -13,65 +13,87 @@
 
 namespace gpf {
 
-// LDS of k_lml_grad: the GEMM's two stages, reused by the epilogue for the tile's coordinates
-// ([d][T] rows | [d][T] columns, d <= DMAX: exactly DL_STAGE at d = 32), then the squared norms and
-// alpha of the rows and columns, then the waves' partial sums.
-constexpr int LG_VEC = DL_STAGE;           // n_i | n_j | alpha_i | alpha_j, T each
-constexpr int LG_RED = LG_VEC + 4 * T;     // [8 waves][DMAX]
-constexpr int LG_LDS = LG_RED + 8 * DMAX;  // doubles (69.6 KiB: two workgroups per CU)
-static_assert(2 * DMAX * T <= DL_STAGE, "k_lml_grad: the tile's coordinates fit the GEMM stages");
+// The lower tile (I, J <= I) of index idx = I (I + 1) / 2 + J: the root in floating point, then
+// corrected to the exact integers either way
+__device__ __forceinline__ void tri_decode(int idx, int& I, int& J) {
+  I = (int)((sqrt(8.0 * idx + 1.0) - 1.0) * 0.5);
+  while ((I + 1) * (I + 2) / 2 <= idx) ++I;
+  while (I * (I + 1) / 2 > idx) --I;
+  J = idx - I * (I + 1) / 2;
+}
 
-// Lower tile (I, J <= I) of W = U^T U for particle blockIdx.y, reduced against the kernel derivative:
-//   W_IJ = sum_{K >= I} U_KI^T U_KJ, depth (nt - I) 128. Both operands are [k][c] panels of the
-//   row-major U (the TN flavour of the streaming core: nothing is transposed in memory). Tiles K < I
-//   hold zeros (U is lower triangular) and the tiles above the diagonal of d_U are scratch: neither
-//   is read. U's diagonal blocks carry zeros above their diagonal (factor128) and the padded rows are
-//   identity rows (k_build_cov pads K with an identity block), so the padding adds exact zeros to
-//   every W_ij with i, j < N. On the diagonal tiles only the lower triangle is formed (TRI_C_LOWER).
-// Epilogue, per element j < i < N: K_ij recomputed from x and l with k_build_cov's operation order
-// (d_L holds L by now), w = (alpha_i alpha_j - W_ij) K_ij, then per coordinate k
+// The same tiles with the nt (nt - 1) / 2 below the diagonal first (idx = I (I - 1) / 2 + J, J < I) and
+// the nt diagonal tiles after them: for launches whose diagonal tiles are the lighter ones
+__device__ __forceinline__ void tri_decode_offdiag_first(int idx, int nt, int& I, int& J) {
+  const int noff = nt * (nt - 1) / 2;
+  if (idx < noff) {
+    tri_decode(idx, I, J);
+    ++I;
+  } else {
+    I = J = idx - noff;
+  }
+}
+
+// acc = A[:, I]^T A[:, J] over `depth` rows of the row-major A (leading dimension ld): both operands
+// are [k][c] panels (the TN flavour of the streaming core: nothing is transposed in memory). On a
+// diagonal tile only the lower triangle is formed (TRI_C_LOWER). Both panels are re-read by other
+// tiles of the launch: default cache policy. Ends with a barrier: the stages are free afterwards.
+__device__ __forceinline__ void gram_tile(Acc<T>& acc, const double* A, int ld, int I, int J, int depth, double* smem,
+                                          const Quad<T>& qd) {
+  acc.zero();
+  if (I == J)
+    gemm_stream_dl<true, false, TRI_C_LOWER, 2, false, true>(acc, A + (size_t)I * T, ld, A + (size_t)J * T, ld, depth, smem, qd);
+  else
+    gemm_stream_dl<true, false, TRI_NONE, 2, false, true>(acc, A + (size_t)I * T, ld, A + (size_t)J * T, ld, depth, smem, qd);
+}
+
+// Lower tile blockIdx.x = I (I + 1) / 2 + J of W = U^T U for particle blockIdx.y (ascending I, so the
+// deepest tiles are dispatched first): W_IJ = sum_{K >= I} U_KI^T U_KJ, depth (nt - I) 128. Tiles K < I
+// hold zeros (U is lower triangular) and the tiles above the diagonal of d_U are scratch: neither is
+// read. U's diagonal blocks carry zeros above their diagonal (factor128) and the padded rows are
+// identity rows (k_build_cov pads K with an identity block), so the padding adds exact zeros to every
+// W_ij with i, j < N.
+__device__ __forceinline__ void w_tile(Acc<T>& acc, int& I, int& J, int Npad, int nt, const double* U, double* smem,
+                                       const Quad<T>& qd) {
+  tri_decode(blockIdx.x, I, J);
+  const double* Up = U + (size_t)blockIdx.y * Npad * Npad + (size_t)I * T * Npad;  // block row I: the first K
+  gram_tile(acc, Up, Npad, I, J, (nt - I) * T, smem, qd);
+}
+
+// LDS of a gradient kernel with NV per-point vectors besides the squared norms (k_lml_grad: alpha;
+// k_loo_grad: alpha, u): the GEMM's two stages, reused by the epilogue for the tile's coordinates
+// ([d][T] rows | [d][T] columns, d <= DMAX: exactly DL_STAGE at d = 32), then n_i | n_j and the rows and
+// columns of each vector (T each), then the waves' partial sums. In doubles.
+template <int NV>
+struct GradLds {
+  static constexpr int VEC = DL_STAGE;
+  static constexpr int RED = VEC + (2 + 2 * NV) * T;  // [8 waves][DMAX]
+  static constexpr int LDS = RED + 8 * DMAX;          // NV = 1: 69.6 KiB, NV = 2: 71.6 KiB (two workgroups per CU)
+};
+static_assert(2 * DMAX * T <= DL_STAGE, "grad_epilogue: the tile's coordinates fit the GEMM stages");
+
+// The epilogue of k_lml_grad and k_loo_grad: acc holds tile (I, J <= I) of a symmetric matrix M for
+// particle p (after a GEMM that ended with a barrier), and for every element j < i < N
+//   w_ij = weight(rows' vectors at i, columns' vectors at j, M_ij) K_ij,
+// K_ij the noise-free kernel value recomputed from x and the particle's length scales lp with
+// k_build_cov's operation order (d_L holds L by now). Then per coordinate k
 //   partial[p][tile][k] = sum_ij w_ij (x_ik - x_jk)^2
 // summed in a fixed order: per lane over its 32 rows (ascending), over the 4 lane groups
 // (sum_lane_groups), over the wave's 16 columns (xor 8, 4, 2, 1), over the 8 waves in wave order. No
 // floating-point atomics: the same inputs give the same bits.
-// Tile index blockIdx.x = I (I + 1) / 2 + J: ascending I, so the deepest tiles are dispatched first.
-// grid: (nt (nt + 1) / 2, particles)
-__global__ __launch_bounds__(Geo<T>::NTH, 4) void k_lml_grad(int N, int Npad, int nt, int d,
-                                                             const double* __restrict__ x,
-                                                             const double* __restrict__ ls,
-                                                             const double* __restrict__ U,
-                                                             const double* __restrict__ alpha,
-                                                             double* __restrict__ partial) {
-  __shared__ __attribute__((aligned(16))) double smem[LG_LDS];
-  const int idx = blockIdx.x, p = blockIdx.y;
-  int I = (int)((sqrt(8.0 * idx + 1.0) - 1.0) * 0.5);
-  while ((I + 1) * (I + 2) / 2 <= idx) ++I;
-  while (I * (I + 1) / 2 > idx) --I;
-  const int J = idx - I * (I + 1) / 2;
-  const Quad<T> qd;
-  Acc<T> acc;
-  acc.zero();
-  {
-    const double* Up = U + (size_t)p * Npad * Npad + (size_t)I * T * Npad;  // block row I: the first K
-    const int depth = (nt - I) * T;
-    // (both panels are re-read by other tiles of the launch: default cache policy)
-    if (I == J)
-      gemm_stream_dl<true, false, TRI_C_LOWER, 2, false, true>(acc, Up + (size_t)I * T, Npad, Up + (size_t)J * T, Npad,
-                                                               depth, smem, qd);
-    else
-      gemm_stream_dl<true, false, TRI_NONE, 2, false, true>(acc, Up + (size_t)I * T, Npad, Up + (size_t)J * T, Npad,
-                                                            depth, smem, qd);
-  }
-  // (the GEMM ends with a barrier: the stages are free)
+// load(v, g): vector v < NV at point g < N. weight(r, c, m): r[v] and c[v] the vectors at the row and
+// at the column.
+template <int NV, typename Load, typename Weight>
+__device__ __forceinline__ void grad_epilogue(Acc<T>& acc, const Quad<T>& qd, double* smem, int I, int J, int p, int N, int d,
+                                              const double* __restrict__ x, const double* __restrict__ lp, Load load,
+                                              Weight weight, double* __restrict__ partial) {
   const int tid = threadIdx.x;
-  const double* lp = ls + (size_t)p * d;
   double* sa = smem;          // [d][T] rows (block I): scaled coordinates, then the raw ones
   double* sb = smem + d * T;  // [d][T] columns (block J)
-  double* na = smem + LG_VEC;
+  double* na = smem + GradLds<NV>::VEC;
   double* nb = na + T;
-  double* ali = nb + T;
-  double* alj = ali + T;
-  double* red = smem + LG_RED;
+  double* vec = nb + T;  // vector v: rows at vec + 2 v T, columns T behind them
+  double* red = smem + GradLds<NV>::RED;
   if (tid < 2 * T) {  // as cov_tile_acc: a = x / l, |a|^2 summed over the coordinates in order
     const int t = tid & (T - 1);
     const bool rows = tid < T;
@@ -88,14 +110,18 @@ __global__ __launch_bounds__(Geo<T>::NTH, 4) void k_lml_grad(int N, int Npad, in
       for (int k = 0; k < d; ++k) a[k * T + t] = 0.0;  // (padding: finite, masked below)
     }
     (rows ? na : nb)[t] = nrm;
-    (rows ? ali : alj)[t] = g < N ? alpha[(size_t)p * Npad + g] : 0.0;
+#pragma unroll
+    for (int v = 0; v < NV; ++v) vec[(2 * v + (rows ? 0 : 1)) * T + t] = g < N ? load(v, g) : 0.0;
   }
   __syncthreads();
   static_assert(Acc<T>::MBC == 1, "one column per lane");
   constexpr int MBR = Acc<T>::MBR;
   const int col = qd.col(0), gj = J * T + col;
   {
-    const double nc = nb[col], aj = alj[col], b0 = sb[col];
+    const double nc = nb[col], b0 = sb[col];
+    double cv[NV], rv[NV];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) cv[v] = vec[(2 * v + 1) * T + col];
 #pragma unroll
     for (int mi = 0; mi < MBR; ++mi) {
       double dot[4];
@@ -112,7 +138,9 @@ __global__ __launch_bounds__(Geo<T>::NTH, 4) void k_lml_grad(int N, int Npad, in
         const int row = qd.row(mi, r), gi = I * T + row;
         double r2 = (na[row] + nc) - 2.0 * dot[r];
         r2 = r2 > 0.0 ? r2 : 0.0;  // np.maximum(sq_dist, 0)
-        const double w = (ali[row] * aj - acc.v[mi][0][r]) * exp(-0.5 * r2);
+#pragma unroll
+        for (int v = 0; v < NV; ++v) rv[v] = vec[2 * v * T + row];
+        const double w = weight(rv, cv, acc.v[mi][0][r]) * exp(-0.5 * r2);
         double wm = (gj < gi && gi < N) ? w : 0.0;
         // (formed here: left to the optimiser, the 32 exponentials sink past the barriers below into the
         // coordinate loop's preheader, and their 32 arguments spill on the way)
@@ -156,8 +184,30 @@ __global__ __launch_bounds__(Geo<T>::NTH, 4) void k_lml_grad(int N, int Npad, in
     double s = red[tid];
 #pragma unroll
     for (int w = 1; w < 8; ++w) s = s + red[w * DMAX + tid];
-    partial[((size_t)p * gridDim.x + idx) * d + tid] = s;
+    partial[((size_t)p * gridDim.x + blockIdx.x) * d + tid] = s;
   }
+}
+
+// GEMM: lower tile (I, J <= I) of W = U^T U for particle blockIdx.y (w_tile), never stored.
+// Weight: (alpha_i alpha_j - W_ij) K_ij (grad_epilogue).
+// Tile order: blockIdx.x = I (I + 1) / 2 + J, the deepest tiles first.
+// grid: (nt (nt + 1) / 2, particles)
+__global__ __launch_bounds__(Geo<T>::NTH, 4) void k_lml_grad(int N, int Npad, int nt, int d,
+                                                             const double* __restrict__ x,
+                                                             const double* __restrict__ ls,
+                                                             const double* __restrict__ U,
+                                                             const double* __restrict__ alpha,
+                                                             double* __restrict__ partial) {
+  __shared__ __attribute__((aligned(16))) double smem[GradLds<1>::LDS];
+  const int p = blockIdx.y;
+  int I, J;
+  const Quad<T> qd;
+  Acc<T> acc;
+  w_tile(acc, I, J, Npad, nt, U, smem, qd);
+  const double* ap = alpha + (size_t)p * Npad;
+  grad_epilogue<1>(
+      acc, qd, smem, I, J, p, N, d, x, ls + (size_t)p * d, [&](int, int g) { return ap[g]; },
+      [](const double* ri, const double* cj, double w) { return ri[0] * cj[0] - w; }, partial);
 }
 
 // alpha_c = sum_t szp[p][t][c] over row tiles t >= c / 128, for every particle of the chunk

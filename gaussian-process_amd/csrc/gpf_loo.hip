@@ -14,6 +14,7 @@
 // registers against the kernel derivative (k_loo_grad), as k_lml_grad reduces W.
 #pragma once
 #include "gpf_common.hip"
+#include "gpf_lmlgrad.hip"  // tri_decode, gram_tile, w_tile, grad_epilogue
 #include "gpf_postcov.hip"  // MIR_B
 
 namespace gpf {
@@ -74,30 +75,17 @@ __global__ __launch_bounds__(NTHR) void k_loo_points(int N, int Npad, int nt, co
 }
 
 // Lower tile (I, J <= I) of W = U^T U for particle blockIdx.y, stored into the particle's Npad x Npad
-// row-major matrix at Wm: k_lml_grad's GEMM call unchanged (depth (nt - I) 128, TRI_C_LOWER on the
-// diagonal tiles, tile index I (I + 1) / 2 + J so the deepest tiles are dispatched first), with a
-// store of the tile in place of the reduction. What a diagonal tile holds above its diagonal is not
-// read (k_loo_scale_mirror takes the lower triangle only). grid: (nt (nt + 1) / 2, particles)
+// row-major matrix at Wm: k_lml_grad's GEMM and tile order (w_tile), with a store of the tile in place
+// of the reduction. What a diagonal tile holds above its diagonal is not read (k_loo_scale_mirror takes
+// the lower triangle only). grid: (nt (nt + 1) / 2, particles)
 __global__ __launch_bounds__(Geo<T>::NTH, 4) void k_loo_w(int Npad, int nt, const double* __restrict__ U,
                                                           double* __restrict__ Wm) {
   __shared__ __attribute__((aligned(16))) double smem[DL_STAGE];
-  const int idx = blockIdx.x, p = blockIdx.y;
-  int I = (int)((sqrt(8.0 * idx + 1.0) - 1.0) * 0.5);
-  while ((I + 1) * (I + 2) / 2 <= idx) ++I;
-  while (I * (I + 1) / 2 > idx) --I;
-  const int J = idx - I * (I + 1) / 2;
+  int I, J;
   const Quad<T> qd;
   Acc<T> acc;
-  acc.zero();
-  const double* Up = U + (size_t)p * Npad * Npad + (size_t)I * T * Npad;  // block row I: the first K
-  const int depth = (nt - I) * T;
-  if (I == J)
-    gemm_stream_dl<true, false, TRI_C_LOWER, 2, false, true>(acc, Up + (size_t)I * T, Npad, Up + (size_t)J * T, Npad, depth,
-                                                             smem, qd);
-  else
-    gemm_stream_dl<true, false, TRI_NONE, 2, false, true>(acc, Up + (size_t)I * T, Npad, Up + (size_t)J * T, Npad, depth,
-                                                          smem, qd);
-  acc.store(qd, Wm + (size_t)p * Npad * Npad + (size_t)I * T * Npad + (size_t)J * T, (size_t)Npad);
+  w_tile(acc, I, J, Npad, nt, U, smem, qd);
+  acc.store(qd, Wm + (size_t)blockIdx.y * Npad * Npad + (size_t)I * T * Npad + (size_t)J * T, (size_t)Npad);
 }
 
 // B = diag(sqrt g) W, dense and in place: the 64x64 block (bi, bj <= bi) of the stored lower triangle
@@ -111,10 +99,8 @@ __global__ __launch_bounds__(NTHR) void k_loo_scale_mirror(int N, int Npad, doub
                                                            const double* __restrict__ vec) {
   __shared__ double s[MIR_B][MIR_B + 1];
   const int idx = blockIdx.x, p = blockIdx.y, tid = threadIdx.x;
-  int bi = (int)((sqrt(8.0 * idx + 1.0) - 1.0) * 0.5);
-  while ((bi + 1) * (bi + 2) / 2 <= idx) ++bi;
-  while (bi * (bi + 1) / 2 > idx) --bi;
-  const int bj = idx - bi * (bi + 1) / 2;
+  int bi, bj;
+  tri_decode(idx, bi, bj);
   double* Bp = Bm + (size_t)p * Npad * Npad;
   const double* sg = vec + ((size_t)p * LV_N + LV_SG) * Npad;
   const int c = tid & (MIR_B - 1), r0 = tid >> 6;  // 4 rows per pass
@@ -154,22 +140,12 @@ __global__ __launch_bounds__(NTHR) void k_loo_u(int N, int Npad, const double* _
   if (q == 0) vp[(size_t)LV_U * Npad + a] = a < N ? (sq[c] + sq[64 + c]) + (sq[128 + c] + sq[192 + c]) : 0.0;
 }
 
-// LDS of k_loo_grad: k_lml_grad's layout with six T-vectors (n, alpha and u of the rows and columns)
-constexpr int LOO_VEC = DL_STAGE;            // n_i | n_j | alpha_i | alpha_j | u_i | u_j, T each
-constexpr int LOO_RED = LOO_VEC + 6 * T;     // [8 waves][DMAX]
-constexpr int LOO_LDS = LOO_RED + 8 * DMAX;  // doubles (71.6 KiB: two workgroups per CU)
-static_assert(2 * DMAX * T <= DL_STAGE, "k_loo_grad: the tile's coordinates fit the GEMM stages");
-
-// Lower tile (I, J <= I) of G = B^T B for particle blockIdx.y, reduced against the kernel derivative:
-//   G_IJ = B[:, I]^T B[:, J] over the full depth Npad, both operands [k][c] panels of the row-major B
-//   (the call k_post_cov makes on V). B's padding holds exact zeros.
-// Epilogue: k_lml_grad's with the weight (u_i alpha_j + u_j alpha_i - 2 G_ij) K_ij: K_ij recomputed
-// in k_build_cov's operation order, one exp in flight at a time, then per coordinate k
-//   partial[p][tile][k] = sum_{j < i < N} w_ij (x_ik - x_jk)^2
-// in k_lml_grad's fixed order (per lane over its 32 rows, the 4 lane groups, the wave's 16 columns,
-// the 8 waves). No floating-point atomics. k_lml_grad_sum finishes the sum over the tiles.
-// Tile order: all depths are equal, so the nt (nt - 1) / 2 tiles below the diagonal go first
-// (blockIdx.x = I (I - 1) / 2 + J) and the lighter diagonal tiles last, as k_post_cov.
+// GEMM: lower tile (I, J <= I) of G = B^T B for particle blockIdx.y over the full depth Npad (the call
+// k_post_cov makes on V; B's padding holds exact zeros), never stored.
+// Weight: (u_i alpha_j + u_j alpha_i - 2 G_ij) K_ij (grad_epilogue; k_lml_grad_sum finishes the sum
+// over the tiles).
+// Tile order: all depths are equal, so the tiles below the diagonal go first and the lighter diagonal
+// tiles last (tri_decode_offdiag_first), as k_post_cov.
 // grid: (nt (nt + 1) / 2, particles)
 __global__ __launch_bounds__(Geo<T>::NTH, 4) void k_loo_grad(int N, int Npad, int nt, int d,
                                                              const double* __restrict__ x,
@@ -177,129 +153,18 @@ __global__ __launch_bounds__(Geo<T>::NTH, 4) void k_loo_grad(int N, int Npad, in
                                                              const double* __restrict__ Bm,
                                                              const double* __restrict__ vec,
                                                              double* __restrict__ partial) {
-  __shared__ __attribute__((aligned(16))) double smem[LOO_LDS];
-  const int idx = blockIdx.x, p = blockIdx.y, noff = nt * (nt - 1) / 2;
+  __shared__ __attribute__((aligned(16))) double smem[GradLds<2>::LDS];
+  const int p = blockIdx.y;
   int I, J;
-  if (idx < noff) {
-    I = (int)((sqrt(8.0 * idx + 1.0) + 1.0) * 0.5);
-    while (I * (I + 1) / 2 <= idx) ++I;
-    while (I * (I - 1) / 2 > idx) --I;
-    J = idx - I * (I - 1) / 2;
-  } else {
-    I = J = idx - noff;
-  }
+  tri_decode_offdiag_first(blockIdx.x, nt, I, J);
   const Quad<T> qd;
   Acc<T> acc;
-  acc.zero();
-  {
-    const double* Bp = Bm + (size_t)p * Npad * Npad;
-    if (I == J)
-      gemm_stream_dl<true, false, TRI_C_LOWER, 2, false, true>(acc, Bp + (size_t)I * T, Npad, Bp + (size_t)J * T, Npad, Npad,
-                                                               smem, qd);
-    else
-      gemm_stream_dl<true, false, TRI_NONE, 2, false, true>(acc, Bp + (size_t)I * T, Npad, Bp + (size_t)J * T, Npad, Npad,
-                                                            smem, qd);
-  }
-  // (the GEMM ends with a barrier: the stages are free)
-  const int tid = threadIdx.x;
-  const double* lp = ls + (size_t)p * d;
+  gram_tile(acc, Bm + (size_t)p * Npad * Npad, Npad, I, J, Npad, smem, qd);
   const double* vp = vec + (size_t)p * LV_N * Npad;
-  double* sa = smem;          // [d][T] rows (block I): scaled coordinates, then the raw ones
-  double* sb = smem + d * T;  // [d][T] columns (block J)
-  double* na = smem + LOO_VEC;
-  double* nb = na + T;
-  double* ali = nb + T;
-  double* alj = ali + T;
-  double* ui = alj + T;
-  double* uj = ui + T;
-  double* red = smem + LOO_RED;
-  if (tid < 2 * T) {  // as cov_tile_acc: a = x / l, |a|^2 summed over the coordinates in order
-    const int t = tid & (T - 1);
-    const bool rows = tid < T;
-    const int g = (rows ? I : J) * T + t;
-    double* a = rows ? sa : sb;
-    double nrm = 0.0;
-    if (g < N) {
-      for (int k = 0; k < d; ++k) {
-        const double v = x[(size_t)k * N + g] / lp[k];
-        a[k * T + t] = v;
-        nrm = nrm + v * v;
-      }
-    } else {
-      for (int k = 0; k < d; ++k) a[k * T + t] = 0.0;  // (padding: finite, masked below)
-    }
-    (rows ? na : nb)[t] = nrm;
-    (rows ? ali : alj)[t] = g < N ? vp[(size_t)LV_ALPHA * Npad + g] : 0.0;
-    (rows ? ui : uj)[t] = g < N ? vp[(size_t)LV_U * Npad + g] : 0.0;
-  }
-  __syncthreads();
-  static_assert(Acc<T>::MBC == 1, "one column per lane");
-  constexpr int MBR = Acc<T>::MBR;
-  const int col = qd.col(0), gj = J * T + col;
-  {
-    const double nc = nb[col], aj = alj[col], vj = uj[col], b0 = sb[col];
-#pragma unroll
-    for (int mi = 0; mi < MBR; ++mi) {
-      double dot[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) dot[r] = sa[qd.row(mi, r)] * b0;
-      for (int k = 1; k < d; ++k) {
-        const double bk = sb[k * T + col];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) dot[r] = fma(sa[k * T + qd.row(mi, r)], bk, dot[r]);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = qd.row(mi, r), gi = I * T + row;
-        double r2 = (na[row] + nc) - 2.0 * dot[r];
-        r2 = r2 > 0.0 ? r2 : 0.0;  // np.maximum(sq_dist, 0)
-        const double w = ((ui[row] * aj + vj * ali[row]) - 2.0 * acc.v[mi][0][r]) * exp(-0.5 * r2);
-        double wm = (gj < gi && gi < N) ? w : 0.0;
-        // (formed here, as in k_lml_grad: left to the optimiser the exponentials sink into the
-        // coordinate loop's preheader and their arguments spill)
-        asm volatile("" : "+v"(wm));
-        acc.v[mi][0][r] = wm;
-        __builtin_amdgcn_sched_barrier(0);  // (one exp at a time, as cov_tile_acc)
-      }
-    }
-  }
-  __syncthreads();
-  if (tid < 2 * T) {  // the raw coordinates replace the scaled ones
-    const int t = tid & (T - 1);
-    const bool rows = tid < T;
-    const int g = (rows ? I : J) * T + t;
-    double* a = rows ? sa : sb;
-    for (int k = 0; k < d; ++k) a[k * T + t] = g < N ? x[(size_t)k * N + g] : 0.0;
-  }
-  __syncthreads();
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  for (int k = 0; k < d; ++k) {
-    const double bk = sb[k * T + col];
-    double s = 0.0;
-#pragma unroll
-    for (int mi = 0; mi < MBR; ++mi) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const double df = sa[k * T + qd.row(mi, r)] - bk;
-        s = fma(acc.v[mi][0][r], df * df, s);
-      }
-      __builtin_amdgcn_sched_barrier(0);  // (the row reads in groups of 4: not all 32 in flight)
-    }
-    s = sum_lane_groups(s);
-    s = s + __shfl_xor(s, 8);
-    s = s + __shfl_xor(s, 4);
-    s = s + __shfl_xor(s, 2);
-    s = s + __shfl_xor(s, 1);
-    if (qd.lane == 0) red[wave * DMAX + k] = s;
-  }
-  __syncthreads();
-  if (tid < d) {
-    double s = red[tid];
-#pragma unroll
-    for (int w = 1; w < 8; ++w) s = s + red[w * DMAX + tid];
-    partial[((size_t)p * gridDim.x + idx) * d + tid] = s;
-  }
+  grad_epilogue<2>(
+      acc, qd, smem, I, J, p, N, d, x, ls + (size_t)p * d,
+      [&](int v, int g) { return vp[(size_t)(v == 0 ? LV_ALPHA : LV_U) * Npad + g]; },
+      [](const double* ri, const double* cj, double m) { return (ri[1] * cj[0] + cj[1] * ri[0]) - 2.0 * m; }, partial);
 }
 
 }  // namespace gpf

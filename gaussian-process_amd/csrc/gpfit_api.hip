@@ -15,6 +15,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -2029,6 +2030,96 @@ int gpf_log_marginal_likelihood(gpf_ctx* c, const double* ls, double* out) {
   return GPF_OK;
 }
 
+// ---- the batched objectives over the chunk workspace: gpf_lml_batch, gpf_loo_batch, gpf_lml_hyper_batch ----
+
+// The flops of W = U^T U on the lower tiles, the same N^3/3 as the factorisation: the sum over the
+// tiles (I, J <= I) of 2 T^3 (nt - I) (k_lml_grad, k_loo_w)
+static double tri_gemm_flops(int nt) {
+  double fl = 0.0;
+  for (int I = 0; I < nt; ++I) fl += 2.0 * (double)T * T * T * (double)(nt - I) * (I + 1);
+  return fl;
+}
+
+// One batched objective call: what objective_batch needs from its entry point. The hooks run once
+// per pass of pc particles starting at particle s, on c->stream; q is a particle's slot in its pass.
+struct Objective {
+  const double* rows;  // particle p's d length scales at rows + p * stride
+  int stride;
+  int P, pass;                   // particles, and particles per pass (<= c->cap)
+  const double* nfac = nullptr;  // run_factor's per-slot noise factors (filled by `upload`), or none
+  double* value;                 // [P]: -inf for a particle whose matrix is not positive definite
+  const double* hval;            // where `fetch` leaves slot q's value on the host: hval[q * hstride]
+  int hstride;
+  double* grad = nullptr;  // null: no gradient. Particle p's d length-scale derivatives at grad + p * gstride
+  int gstride = 0;
+  double grad_flops = 0.0;  // per particle, of `tiles`
+  int* status;
+  int* bad_idx;
+  std::function<int(int s, int pc)> upload;  // optional: what the pass needs on the device before its factorisation
+  std::function<int(int pc)> enqueue;        // the value kernels and, with the gradient, what precedes `tiles`
+  // the kernel that reduces every lower tile to partial[pc][nt (nt + 1) / 2][d] (a bare launch:
+  // objective_batch brackets it together with k_lml_grad_sum)
+  std::function<void(int pc, double* partial)> tiles;
+  std::function<int(int s, int pc)> fetch;              // the pass's results to the host (hval and the call's own outputs)
+  std::function<void(int p, int q, bool bad)> outputs;  // optional: the call's own per-particle outputs
+};
+
+// The passes of a batched objective: stage the length scales, factorise, run the call's kernels, finish
+// the gradient (the sum over the tiles and 1 / l^3: k_lml_grad_sum), bring the results and the factors'
+// info words back, and fold them particle by particle. A particle whose matrix is not positive definite
+// gets status GPF_NOT_PD, value -inf and a NaN gradient row; the first one sets the return value and
+// *bad_idx, and the batch goes on. The caller has sized the workspace (ensure_work).
+static int objective_batch(gpf_ctx* c, const Knobs& knobs, const Objective& o) {
+  const int d = c->d, ntile = c->nt * (c->nt + 1) / 2;
+  double* d_grad = nullptr;
+  std::vector<double> hg;
+  if (o.grad) {
+    // per-tile partials, then the gradient rows
+    // (synchronised regrow: the previous call's gradient pass may still be reading it)
+    if (int rc = c->gpart.grow(c, ((size_t)o.pass * ntile * d + (size_t)o.pass * d) * 8, false, true)) return rc;
+    d_grad = c->gpart.as<double>() + (size_t)o.pass * ntile * d;
+    hg.resize((size_t)o.pass * d);
+  }
+  int ret = GPF_OK, rc;
+  for (int s = 0; s < o.P; s += o.pass) {
+    const int pc = std::min(o.pass, o.P - s);
+    for (int q = 0; q < pc; ++q) std::memcpy(c->h_ls + (size_t)q * d, o.rows + (size_t)(s + q) * o.stride, (size_t)d * 8);
+    GPF_HIP(c, hipMemcpyAsync(c->d_ls, c->h_ls, (size_t)pc * d * 8, hipMemcpyHostToDevice, c->stream));
+    if (o.upload && (rc = o.upload(s, pc))) return rc;
+    if ((rc = run_factor(c, pc, knobs, o.nfac))) return rc;
+    if ((rc = o.enqueue(pc))) return rc;
+    if (o.grad) {
+      rc = launch(c, PC_LOSS, o.grad_flops * pc, [&] {
+        o.tiles(pc, c->gpart.as<double>());
+        hipLaunchKernelGGL(gpf::k_lml_grad_sum, dim3(pc), dim3(gpf::DMAX), 0, c->stream, ntile, d, c->gpart.as<double>(), c->d_ls,
+                           d_grad);
+      });
+      if (rc) return rc;
+      GPF_HIP(c, hipMemcpyAsync(hg.data(), d_grad, (size_t)pc * d * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    if ((rc = o.fetch(s, pc))) return rc;
+    GPF_HIP(c, hipMemcpyAsync(c->h_info, c->d_info, (size_t)pc * 4, hipMemcpyDeviceToHost, c->stream));
+    GPF_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->prof) harvest(c);
+    for (int q = 0; q < pc; ++q) {
+      const int p = s + q;
+      const int st = particle_status(c, q);
+      if (st == GPF_HIP_ERROR) return st;
+      const bool bad = st != GPF_OK;
+      if (bad && ret == GPF_OK) {
+        ret = GPF_NOT_PD;
+        if (o.bad_idx) *o.bad_idx = p;
+      }
+      if (o.status) o.status[p] = bad ? GPF_NOT_PD : GPF_OK;
+      o.value[p] = bad ? -INFINITY : o.hval[(size_t)q * o.hstride];
+      if (o.grad)
+        for (int k = 0; k < d; ++k) o.grad[(size_t)p * o.gstride + k] = bad ? NAN : hg[(size_t)q * d + k];
+      if (o.outputs) o.outputs(p, q, bad);
+    }
+  }
+  return ret;
+}
+
 int gpf_lml_batch(gpf_ctx* c, const double* ls, int P, double* lml, double* grad, int* status, int* bad_idx) {
   if (!c) return GPF_BAD_ARG;
   if (bad_idx) *bad_idx = -1;
@@ -2040,67 +2131,30 @@ int gpf_lml_batch(gpf_ctx* c, const double* ls, int P, double* lml, double* grad
   hipSetDevice(c->device);
   const int64_t N = c->N, Np = c->Npad;
   const Knobs knobs = Knobs::from_env();
-  int rc = ensure_work(c, P, knobs);
-  if (rc) return rc;
-  const int cap = c->cap;
-  const int ntile = nt * (nt + 1) / 2;
-  double* d_grad = nullptr;
-  if (grad) {
-    const int pcm = std::min(cap, P);
-    // (synchronised regrow: the previous call's gradient pass may still be reading it)
-    if ((rc = c->gpart.grow(c, ((size_t)pcm * ntile * d + (size_t)pcm * d) * 8, false, true))) return rc;
-    d_grad = c->gpart.as<double>() + (size_t)pcm * ntile * d;
-  }
-  std::vector<double> hg;
-  if (grad) hg.resize((size_t)std::min(cap, P) * d);
-  int ret = GPF_OK;
-  for (int s = 0; s < P; s += cap) {
-    const int pc = std::min(cap, P - s);
-    std::memcpy(c->h_ls, ls + (size_t)s * d, (size_t)pc * d * 8);
-    GPF_HIP(c, hipMemcpyAsync(c->d_ls, c->h_ls, (size_t)pc * d * 8, hipMemcpyHostToDevice, c->stream));
-    rc = run_factor(c, pc, knobs);
-    if (rc) return rc;
-    // alpha into the mu slots, the value into the loss slots of the chunk workspace
-    rc = launch(c, PC_LOSS, 0.0, [&] {
+  if (int rc = ensure_work(c, P, knobs)) return rc;
+  Objective o;
+  o.rows = ls, o.stride = d, o.P = P, o.pass = std::min(c->cap, P);
+  o.value = lml, o.hval = c->h_loss, o.hstride = 1;
+  o.grad = grad, o.gstride = d, o.grad_flops = tri_gemm_flops(nt);
+  o.status = status, o.bad_idx = bad_idx;
+  // alpha into the mu slots, the value into the loss slots of the chunk workspace
+  o.enqueue = [&](int pc) {
+    return launch(c, PC_LOSS, 0.0, [&] {
       hipLaunchKernelGGL(gpf::k_alpha_batch, dim3((unsigned)((N + NTHR - 1) / NTHR), pc), dim3(NTHR), 0, c->stream, (int)N,
                          (int)Np, nt, c->d_szp, c->d_mu);
       hipLaunchKernelGGL(gpf::k_lml_value, dim3(pc), dim3(NTHR), 0, c->stream, (int)N, (int)Np, c->d_y, c->d_mu, c->d_L,
                          c->d_loss);
     });
-    if (rc) return rc;
-    if (grad) {
-      // the same N^3/3 flops as the factorisation: sum over the lower tiles (I, J) of 2 T^3 (nt - I)
-      double fl = 0.0;
-      for (int I = 0; I < nt; ++I) fl += 2.0 * (double)T * T * T * (double)(nt - I) * (I + 1);
-      rc = launch(c, PC_LOSS, fl * pc, [&] {
-        hipLaunchKernelGGL(gpf::k_lml_grad, dim3((unsigned)ntile, pc), dim3(gpf::Geo<T>::NTH), 0, c->stream, (int)N,
-                           (int)Np, nt, d, c->d_x, c->d_ls, c->d_U, c->d_mu, c->gpart.as<double>());
-        hipLaunchKernelGGL(gpf::k_lml_grad_sum, dim3(pc), dim3(gpf::DMAX), 0, c->stream, ntile, d, c->gpart.as<double>(), c->d_ls,
-                           d_grad);
-      });
-      if (rc) return rc;
-      GPF_HIP(c, hipMemcpyAsync(hg.data(), d_grad, (size_t)pc * d * 8, hipMemcpyDeviceToHost, c->stream));
-    }
+  };
+  o.tiles = [&](int pc, double* partial) {
+    hipLaunchKernelGGL(gpf::k_lml_grad, dim3((unsigned)(nt * (nt + 1) / 2), pc), dim3(gpf::Geo<T>::NTH), 0, c->stream, (int)N,
+                       (int)Np, nt, d, c->d_x, c->d_ls, c->d_U, c->d_mu, partial);
+  };
+  o.fetch = [&](int, int pc) -> int {
     GPF_HIP(c, hipMemcpyAsync(c->h_loss, c->d_loss, (size_t)pc * 8, hipMemcpyDeviceToHost, c->stream));
-    GPF_HIP(c, hipMemcpyAsync(c->h_info, c->d_info, (size_t)pc * 4, hipMemcpyDeviceToHost, c->stream));
-    GPF_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->prof) harvest(c);
-    for (int q = 0; q < pc; ++q) {
-      const int p = s + q;
-      const int st = particle_status(c, q);
-      if (st == GPF_HIP_ERROR) return st;
-      const bool bad = st != GPF_OK;
-      if (bad && ret == GPF_OK) {
-        ret = GPF_NOT_PD;
-        if (bad_idx) *bad_idx = p;
-      }
-      if (status) status[p] = bad ? GPF_NOT_PD : GPF_OK;
-      lml[p] = bad ? -INFINITY : c->h_loss[q];
-      if (grad)
-        for (int k = 0; k < d; ++k) grad[(size_t)p * d + k] = bad ? NAN : hg[(size_t)q * d + k];
-    }
-  }
-  return ret;
+    return GPF_OK;
+  };
+  return objective_batch(c, knobs, o);
 }
 
 // ---- gpf_loo_batch: leave-one-out predictions, their log predictive density and its gradient ----
@@ -2138,53 +2192,37 @@ int gpf_loo_batch(gpf_ctx* c, const double* ls, int P, double* lpd, double* grad
   if ((rc = c->loo.grow(c, (size_t)pcm * per, false, true))) return rc;
   double* d_vec = c->loo.as<double>();
   double* d_B = d_vec + (size_t)pcm * gpf::LV_N * Np;
-  double* d_grad = nullptr;
-  std::vector<double> hg;
-  if (grad) {
-    // (synchronised regrow: the previous call's gradient pass may still be reading it)
-    if ((rc = c->gpart.grow(c, ((size_t)pcm * ntile * d + (size_t)pcm * d) * 8, false, true))) return rc;
-    d_grad = c->gpart.as<double>() + (size_t)pcm * ntile * d;
-    hg.resize((size_t)pcm * d);
-  }
   const size_t vpitch = (size_t)gpf::LV_N * Np * 8;
-  int ret = GPF_OK;
-  for (int s = 0; s < P; s += pcm) {
-    const int pc = std::min(pcm, P - s);
-    std::memcpy(c->h_ls, ls + (size_t)s * d, (size_t)pc * d * 8);
-    GPF_HIP(c, hipMemcpyAsync(c->d_ls, c->h_ls, (size_t)pc * d * 8, hipMemcpyHostToDevice, c->stream));
-    rc = run_factor(c, pc, knobs);
-    if (rc) return rc;
+  Objective o;
+  o.rows = ls, o.stride = d, o.P = P, o.pass = pcm;
+  o.value = lpd, o.hval = c->h_loss, o.hstride = 1;
+  // G = B^T B reduced against the kernel derivative: every lower tile over the full depth, 2 T^3 nt
+  o.grad = grad, o.gstride = d, o.grad_flops = 2.0 * (double)T * T * T * nt * (double)ntile;
+  o.status = status, o.bad_idx = bad_idx;
+  o.enqueue = [&](int pc) {
     // the per-point quantities into the call's vectors, the density into the loss slots of the workspace
-    rc = launch(c, PC_LOSS, 0.0, [&] {
+    int rc = launch(c, PC_LOSS, 0.0, [&] {
       hipLaunchKernelGGL(gpf::k_loo_points, dim3(pc), dim3(NTHR), 0, c->stream, (int)N, (int)Np, nt, c->d_y, c->d_s2p, c->d_szp,
                          d_vec, c->d_loss);
     });
+    if (rc || !grad) return rc;
+    // W = U^T U, then B = diag(sqrt g) W mirrored to the full matrix and u = W c
+    rc = launch(c, PC_LOSS, tri_gemm_flops(nt) * pc, [&] {
+      hipLaunchKernelGGL(gpf::k_loo_w, dim3((unsigned)ntile, pc), dim3(gpf::Geo<T>::NTH), 0, c->stream, (int)Np, nt, c->d_U, d_B);
+    });
     if (rc) return rc;
-    if (grad) {
-      // W = U^T U: k_lml_grad's flops, the sum over the lower tiles (I, J) of 2 T^3 (nt - I)
-      double fl = 0.0;
-      for (int I = 0; I < nt; ++I) fl += 2.0 * (double)T * T * T * (double)(nt - I) * (I + 1);
-      rc = launch(c, PC_LOSS, fl * pc, [&] {
-        hipLaunchKernelGGL(gpf::k_loo_w, dim3((unsigned)ntile, pc), dim3(gpf::Geo<T>::NTH), 0, c->stream, (int)Np, nt, c->d_U, d_B);
-      });
-      if (rc) return rc;
-      const int nmb = (int)(Np / gpf::MIR_B);
-      rc = launch(c, PC_LOSS, 0.0, [&] {
-        hipLaunchKernelGGL(gpf::k_loo_scale_mirror, dim3((unsigned)(nmb * (nmb + 1) / 2), pc), dim3(NTHR), 0, c->stream, (int)N,
-                           (int)Np, d_B, d_vec);
-        hipLaunchKernelGGL(gpf::k_loo_u, dim3((unsigned)nmb, pc), dim3(NTHR), 0, c->stream, (int)N, (int)Np, d_B, d_vec);
-      });
-      if (rc) return rc;
-      // G = B^T B reduced against the kernel derivative: every lower tile over the full depth, 2 T^3 nt
-      rc = launch(c, PC_LOSS, 2.0 * (double)T * T * T * nt * (double)ntile * pc, [&] {
-        hipLaunchKernelGGL(gpf::k_loo_grad, dim3((unsigned)ntile, pc), dim3(gpf::Geo<T>::NTH), 0, c->stream, (int)N, (int)Np, nt,
-                           d, c->d_x, c->d_ls, d_B, d_vec, c->gpart.as<double>());
-        hipLaunchKernelGGL(gpf::k_lml_grad_sum, dim3(pc), dim3(gpf::DMAX), 0, c->stream, ntile, d, c->gpart.as<double>(), c->d_ls,
-                           d_grad);
-      });
-      if (rc) return rc;
-      GPF_HIP(c, hipMemcpyAsync(hg.data(), d_grad, (size_t)pc * d * 8, hipMemcpyDeviceToHost, c->stream));
-    }
+    const int nmb = (int)(Np / gpf::MIR_B);
+    return launch(c, PC_LOSS, 0.0, [&] {
+      hipLaunchKernelGGL(gpf::k_loo_scale_mirror, dim3((unsigned)(nmb * (nmb + 1) / 2), pc), dim3(NTHR), 0, c->stream, (int)N,
+                         (int)Np, d_B, d_vec);
+      hipLaunchKernelGGL(gpf::k_loo_u, dim3((unsigned)nmb, pc), dim3(NTHR), 0, c->stream, (int)N, (int)Np, d_B, d_vec);
+    });
+  };
+  o.tiles = [&](int pc, double* partial) {
+    hipLaunchKernelGGL(gpf::k_loo_grad, dim3((unsigned)ntile, pc), dim3(gpf::Geo<T>::NTH), 0, c->stream, (int)N, (int)Np, nt, d,
+                       c->d_x, c->d_ls, d_B, d_vec, partial);
+  };
+  o.fetch = [&](int s, int pc) -> int {
     if (mu)
       GPF_HIP(c, hipMemcpy2DAsync(mu + (size_t)s * N, (size_t)N * 8, d_vec + (size_t)gpf::LV_MU * Np, vpitch, (size_t)N * 8,
                                   (size_t)pc, hipMemcpyDeviceToHost, c->stream));
@@ -2192,27 +2230,13 @@ int gpf_loo_batch(gpf_ctx* c, const double* ls, int P, double* lpd, double* grad
       GPF_HIP(c, hipMemcpy2DAsync(sd + (size_t)s * N, (size_t)N * 8, d_vec + (size_t)gpf::LV_SD * Np, vpitch, (size_t)N * 8,
                                   (size_t)pc, hipMemcpyDeviceToHost, c->stream));
     GPF_HIP(c, hipMemcpyAsync(c->h_loss, c->d_loss, (size_t)pc * 8, hipMemcpyDeviceToHost, c->stream));
-    GPF_HIP(c, hipMemcpyAsync(c->h_info, c->d_info, (size_t)pc * 4, hipMemcpyDeviceToHost, c->stream));
-    GPF_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->prof) harvest(c);
-    for (int q = 0; q < pc; ++q) {
-      const int p = s + q;
-      const int st = particle_status(c, q);
-      if (st == GPF_HIP_ERROR) return st;
-      const bool bad = st != GPF_OK;
-      if (bad && ret == GPF_OK) {
-        ret = GPF_NOT_PD;
-        if (bad_idx) *bad_idx = p;
-      }
-      if (status) status[p] = bad ? GPF_NOT_PD : GPF_OK;
-      lpd[p] = bad ? -INFINITY : c->h_loss[q];
-      if (grad)
-        for (int k = 0; k < d; ++k) grad[(size_t)p * d + k] = bad ? NAN : hg[(size_t)q * d + k];
-      if (bad && mu) std::fill(mu + (size_t)p * N, mu + (size_t)(p + 1) * N, (double)NAN);
-      if (bad && sd) std::fill(sd + (size_t)p * N, sd + (size_t)(p + 1) * N, (double)NAN);
-    }
-  }
-  return ret;
+    return GPF_OK;
+  };
+  o.outputs = [&](int p, int, bool bad) {
+    if (bad && mu) std::fill(mu + (size_t)p * N, mu + (size_t)(p + 1) * N, (double)NAN);
+    if (bad && sd) std::fill(sd + (size_t)p * N, sd + (size_t)(p + 1) * N, (double)NAN);
+  };
+  return objective_batch(c, knobs, o);
 }
 
 // ---- gpf_lml_hyper_batch: log marginal likelihood and its gradient in (l, a, s) ----
@@ -2223,7 +2247,7 @@ int gpf_lml_hyper_batch(gpf_ctx* c, const double* th, int P, double* lml, double
   if (P < 0 || (P > 0 && (!th || !lml))) return bad_arg(c, "gpf_lml_hyper_batch: bad arguments");
   if (c->N <= 0) return bad_arg(c, "gpf_lml_hyper_batch: call gpf_set_data first");
   const int d = c->d, nt = c->nt, dh = d + 2;
-  // (a, s) and the noise factor r = (s / a)^2 of every particle: they outlive the chunk loop's copies
+  // (a, s) and the noise factor r = (s / a)^2 of every particle: they outlive the passes' copies
   std::vector<double> has((size_t)P * 2), hr((size_t)P);
   for (int p = 0; p < P; ++p) {
     const double* row = th + (size_t)p * dh;
@@ -2244,8 +2268,7 @@ int gpf_lml_hyper_batch(gpf_ctx* c, const double* th, int P, double* lml, double
   const Knobs knobs = Knobs::from_env();
   int rc = ensure_work(c, P, knobs);
   if (rc) return rc;
-  const int cap = c->cap, pcm = std::min(cap, P);
-  const int ntile = nt * (nt + 1) / 2;
+  const int pcm = std::min(c->cap, P);
   // the call's own vectors: (a, s) | k_hyper_value's results | alt | alt / a
   // (synchronised regrow: the previous call's kernels may still be reading it)
   if ((rc = c->hyp.grow(c, ((size_t)pcm * (2 + gpf::HV_N) + 2 * (size_t)pcm * Np) * 8, false, true))) return rc;
@@ -2253,70 +2276,44 @@ int gpf_lml_hyper_batch(gpf_ctx* c, const double* th, int P, double* lml, double
   double* d_out = d_as + (size_t)pcm * 2;
   double* d_al = d_out + (size_t)pcm * gpf::HV_N;
   double* d_sc = d_al + (size_t)pcm * Np;
-  double* d_grad = nullptr;
-  std::vector<double> hg, ho((size_t)pcm * gpf::HV_N);
-  if (grad) {
-    if ((rc = c->gpart.grow(c, ((size_t)pcm * ntile * d + (size_t)pcm * d) * 8, false, true))) return rc;
-    d_grad = c->gpart.as<double>() + (size_t)pcm * ntile * d;
-    hg.resize((size_t)pcm * d);
-  }
-  int ret = GPF_OK;
-  for (int s = 0; s < P; s += cap) {
-    const int pc = std::min(cap, P - s);
-    for (int q = 0; q < pc; ++q) std::memcpy(c->h_ls + (size_t)q * d, th + (size_t)(s + q) * dh, (size_t)d * 8);
-    GPF_HIP(c, hipMemcpyAsync(c->d_ls, c->h_ls, (size_t)pc * d * 8, hipMemcpyHostToDevice, c->stream));
+  std::vector<double> ho((size_t)pcm * gpf::HV_N);
+  Objective o;
+  o.rows = th, o.stride = dh, o.P = P, o.pass = pcm, o.nfac = c->d_nfac;
+  o.value = lml, o.hval = ho.data() + gpf::HV_LML, o.hstride = gpf::HV_N;
+  o.grad = grad, o.gstride = dh, o.grad_flops = tri_gemm_flops(nt);  // k_lml_grad on alt / a
+  o.status = status, o.bad_idx = bad_idx;
+  o.upload = [&](int s, int pc) -> int {
     GPF_HIP(c, hipMemcpyAsync(c->d_nfac, hr.data() + s, (size_t)pc * 8, hipMemcpyHostToDevice, c->stream));
     GPF_HIP(c, hipMemcpyAsync(d_as, has.data() + (size_t)2 * s, (size_t)pc * 2 * 8, hipMemcpyHostToDevice, c->stream));
-    rc = run_factor(c, pc, knobs, c->d_nfac);
-    if (rc) return rc;
-    rc = launch(c, PC_LOSS, 0.0, [&] {
+    return GPF_OK;
+  };
+  o.enqueue = [&](int pc) {
+    return launch(c, PC_LOSS, 0.0, [&] {
       hipLaunchKernelGGL(gpf::k_alpha_batch, dim3((unsigned)((N + NTHR - 1) / NTHR), pc), dim3(NTHR), 0, c->stream, (int)N,
                          (int)Np, nt, c->d_szp, d_al);
       hipLaunchKernelGGL(gpf::k_hyper_value, dim3(pc), dim3(NTHR), 0, c->stream, (int)N, (int)Np, nt, c->d_y, c->d_e, d_al,
                          c->d_L, c->d_s2p, d_as, d_out);
     });
-    if (rc) return rc;
-    if (grad) {
-      // k_lml_grad on alt / a: gpf_lml_batch's flops
-      double fl = 0.0;
-      for (int I = 0; I < nt; ++I) fl += 2.0 * (double)T * T * T * (double)(nt - I) * (I + 1);
-      rc = launch(c, PC_LOSS, fl * pc, [&] {
-        hipLaunchKernelGGL(gpf::k_hyper_scale, dim3((unsigned)((N + NTHR - 1) / NTHR), pc), dim3(NTHR), 0, c->stream, (int)N,
-                           (int)Np, d_al, d_as, d_sc);
-        hipLaunchKernelGGL(gpf::k_lml_grad, dim3((unsigned)ntile, pc), dim3(gpf::Geo<T>::NTH), 0, c->stream, (int)N,
-                           (int)Np, nt, d, c->d_x, c->d_ls, c->d_U, d_sc, c->gpart.as<double>());
-        hipLaunchKernelGGL(gpf::k_lml_grad_sum, dim3(pc), dim3(gpf::DMAX), 0, c->stream, ntile, d, c->gpart.as<double>(), c->d_ls,
-                           d_grad);
-      });
-      if (rc) return rc;
-      GPF_HIP(c, hipMemcpyAsync(hg.data(), d_grad, (size_t)pc * d * 8, hipMemcpyDeviceToHost, c->stream));
-    }
+  };
+  o.tiles = [&](int pc, double* partial) {
+    hipLaunchKernelGGL(gpf::k_hyper_scale, dim3((unsigned)((N + NTHR - 1) / NTHR), pc), dim3(NTHR), 0, c->stream, (int)N,
+                       (int)Np, d_al, d_as, d_sc);
+    hipLaunchKernelGGL(gpf::k_lml_grad, dim3((unsigned)(nt * (nt + 1) / 2), pc), dim3(gpf::Geo<T>::NTH), 0, c->stream, (int)N,
+                       (int)Np, nt, d, c->d_x, c->d_ls, c->d_U, d_sc, partial);
+  };
+  o.fetch = [&](int, int pc) -> int {
     GPF_HIP(c, hipMemcpyAsync(ho.data(), d_out, (size_t)pc * gpf::HV_N * 8, hipMemcpyDeviceToHost, c->stream));
-    GPF_HIP(c, hipMemcpyAsync(c->h_info, c->d_info, (size_t)pc * 4, hipMemcpyDeviceToHost, c->stream));
-    GPF_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->prof) harvest(c);
-    for (int q = 0; q < pc; ++q) {
-      const int p = s + q;
-      const int st = particle_status(c, q);
-      if (st == GPF_HIP_ERROR) return st;
-      const bool bad = st != GPF_OK;
-      if (bad && ret == GPF_OK) {
-        ret = GPF_NOT_PD;
-        if (bad_idx) *bad_idx = p;
-      }
-      if (status) status[p] = bad ? GPF_NOT_PD : GPF_OK;
-      const double* o = ho.data() + (size_t)q * gpf::HV_N;
-      lml[p] = bad ? -INFINITY : o[gpf::HV_LML];
-      if (qout) qout[p] = bad ? NAN : o[gpf::HV_Q];
-      if (grad) {
-        double* g = grad + (size_t)p * dh;
-        for (int k = 0; k < d; ++k) g[k] = bad ? NAN : hg[(size_t)q * d + k];
-        g[d] = bad ? NAN : o[gpf::HV_DA];
-        g[d + 1] = bad ? NAN : o[gpf::HV_DS];
-      }
+    return GPF_OK;
+  };
+  o.outputs = [&](int p, int q, bool bad) {
+    const double* r = ho.data() + (size_t)q * gpf::HV_N;
+    if (qout) qout[p] = bad ? NAN : r[gpf::HV_Q];
+    if (grad) {
+      grad[(size_t)p * dh + d] = bad ? NAN : r[gpf::HV_DA];
+      grad[(size_t)p * dh + d + 1] = bad ? NAN : r[gpf::HV_DS];
     }
-  }
-  return ret;
+  };
+  return objective_batch(c, knobs, o);
 }
 
 // ---- gpf_predict_batch: prediction for a batch of length-scale samples and their mixture ----

@@ -247,6 +247,38 @@ def test_non_pd_particle_does_not_spoil_the_batch(ctx):
     _check("cluster N=1024, clean batch after the failure", after, gafter, want, gwant)
 
 
+def test_non_pd_particle_in_a_later_chunk(monkeypatch):
+    """The singular particle in the second chunk (P = 6 through a workspace capped at 4: row 5 is slot 1
+    of its chunk): its status, -inf, NaN gradient row (all d + 2 components) and NaN Q land at its index in
+    the batch, not at its slot. The same clustered points at N = 300, the cluster in the second tile."""
+    import gpfit
+    from test_gpu import _cluster_data
+    N, c0, P, bad = 300, 144, 6, 5
+    x, y, e = _cluster_data(N, c0)
+    rng = np.random.default_rng(P)
+    a = rng.uniform(0.5, 3.0, size=P)
+    good = np.column_stack([rng.uniform(0.011, 0.02, size=P), a, a * rng.uniform(0.7, 1.5, size=P)])
+    want, gwant = _reference(("cluster", N), x, y, e, good)
+    Q = good.copy()
+    Q[bad, 0] = 0.2
+    others = [p for p in range(P) if p != bad]
+    monkeypatch.setenv("GPF_MAX_CHUNK", "4")
+    c = gpfit.Context(0)
+    try:
+        c.set_data(x, y, e)
+        lml, grad, q = c.lml_hyper_batch(Q, strict=False, want_q=True)
+        assert lml[bad] == -np.inf and np.all(np.isnan(grad[bad])) and np.isnan(q[bad])
+        assert np.all(np.isfinite(lml[others])) and np.all(np.isfinite(grad[others])) and np.all(np.isfinite(q[others]))
+        _check("cluster N=300, non-PD row 5 in chunk 2", lml, grad, want, gwant, rows=others)
+        with pytest.raises(np.linalg.LinAlgError, match="Matrix is not positive definite") as ei:
+            c.lml_hyper_batch(Q)
+        assert ei.value.particle == bad
+        after, gafter = c.lml_hyper_batch(good)
+        _check("cluster N=300, clean batch after the failure", after, gafter, want, gwant)
+    finally:
+        c.close()
+
+
 def test_bad_arguments():
     import gpfit
     c = gpfit.Context(0)

@@ -213,6 +213,35 @@ def test_non_pd_particle_does_not_spoil_the_batch(ctx):
     _check("cluster N=300, clean batch after the failure", _loo(ctx, good), ref)
 
 
+def test_non_pd_particle_in_a_later_chunk(monkeypatch):
+    """The singular particle in the second chunk (P = 6 through a workspace capped at 4: row 5 is slot 1
+    of its chunk): its status, -inf and NaN rows (gradient, mu, sd) land at its index in the batch, not
+    at its slot. The data and particles of the test above (and its reference)."""
+    import gpfit
+    N, c0, P, bad = 300, 144, 6, 5
+    x, y, e = _cluster_at_origin(N, c0)
+    good = np.random.default_rng(P).uniform(0.011, 0.016, size=(P, 1))
+    ref = _reference(("cluster", N), x, y, e, good)
+    Q = good.copy()
+    Q[bad, 0] = 0.2
+    others = [p for p in range(P) if p != bad]
+    monkeypatch.setenv("GPF_MAX_CHUNK", "4")
+    c = gpfit.Context(0)
+    try:
+        c.set_data(x, y, e)
+        got = _loo(c, Q, strict=False)
+        lpd, grad, mu, sd = got
+        assert lpd[bad] == -np.inf and np.all(np.isnan(grad[bad])) and np.all(np.isnan(mu[bad])) and np.all(np.isnan(sd[bad]))
+        assert all(np.all(np.isfinite(a[others])) for a in got)
+        _check("cluster N=300, non-PD row 5 in chunk 2", got, ref, rows=others)
+        with pytest.raises(np.linalg.LinAlgError, match="Matrix is not positive definite") as ei:
+            _loo(c, Q)
+        assert ei.value.particle == bad
+        _check("cluster N=300, clean batch after the failure", _loo(c, good), ref)
+    finally:
+        c.close()
+
+
 def test_bad_arguments():
     import gpfit
     c = gpfit.Context(0)
