@@ -14,7 +14,9 @@ factor on the quoted errors, gpfit.amplitude.fit_hyper, and the prediction with 
 reuses pso_max_points, pso_seed and mle_num_starts and does not combine with hyper_samples),
 mle_num_starts (40) and hyper_samples (K >= 1: the written mean and sd are marginalised over K
 length-scale samples, gpfit.hyper.predict_marginal, instead of taken at the one fitted vector; it
-reuses pso_max_points and pso_seed).
+reuses pso_max_points and pso_seed) and mean_function ("constant", "linear" or "quadratic": a polynomial
+mean with its coefficients integrated out, gpfit.meanfn.fit_mean and GP_mean; valid only with
+len_scale_objective: marginal_likelihood_full).
 """
 from functools import reduce
 from pathlib import Path
@@ -24,7 +26,7 @@ import yaml
 
 from convex_hull import fill_convex_hull
 from find_len_scales import len_scale_opt
-from GP_func import GP, GP_hyper
+from GP_func import GP, GP_hyper, GP_mean
 from read_in import read_yaml
 
 __all__ = ["process_experiment", "write_individual_file", "write_grouped_file", "write_combined_file",
@@ -59,6 +61,26 @@ def _hyper_samples(options_path="options.yaml"):
     return k
 
 
+def _mean_function(options_path="options.yaml"):
+    """options.yaml's mean_function ("constant", "linear" or "quadratic"), or None (absent: the zero-mean
+    model, byte-identical outputs)."""
+    try:
+        with open(options_path, "r") as f:
+            opts = yaml.safe_load(f) or {}
+    except OSError:
+        return None
+    kind = opts.get("mean_function")
+    if kind is None:
+        return None
+    if kind not in ("constant", "linear", "quadratic"):
+        raise ValueError(f"options.yaml: mean_function must be constant, linear or quadratic, not {kind!r}")
+    if opts.get("len_scale_objective") != "marginal_likelihood_full":
+        raise ValueError("options.yaml: mean_function is valid only with len_scale_objective: "
+                         "marginal_likelihood_full (the fit of length scales, amplitude and noise scale), not with "
+                         f"{opts.get('len_scale_objective', 'calibration')!r}")
+    return kind
+
+
 def _marginal(x_known, y_known, e_known, x_fit, ls, k, pso):
     """predict_marginal's mean and sd at K samples around the marginal likelihood's optimum: the fitted
     vector when the fit maximised it, else gpfit.mle.fit_lml's (the swarm's optimum of the calibration
@@ -70,13 +92,18 @@ def _marginal(x_known, y_known, e_known, x_fit, ls, k, pso):
     return mu, sd
 
 
-def _fit_full(x_known, y_known, e_known, progress, pso):
-    """theta = (l.., a, s) of len_scale_objective: marginal_likelihood_full (gpfit.amplitude.fit_hyper)."""
+def _fit_full(x_known, y_known, e_known, progress, pso, mean_function=None):
+    """theta = (l.., a, s) of len_scale_objective: marginal_likelihood_full (gpfit.amplitude.fit_hyper;
+    with a mean function gpfit.meanfn.fit_mean)."""
     import numpy as np
-    from gpfit.amplitude import fit_hyper
     kw = {key: pso[key] for key in ("num_starts", "max_points", "seed") if key in pso}
-    theta, _ = fit_hyper(np.asarray(x_known, dtype=np.float64), np.asarray(y_known, dtype=np.float64),
-                         np.asarray(e_known, dtype=np.float64), verbose=bool(progress), **kw)
+    data = (np.asarray(x_known, dtype=np.float64), np.asarray(y_known, dtype=np.float64),
+            np.asarray(e_known, dtype=np.float64))
+    if mean_function is not None:
+        from gpfit.meanfn import fit_mean
+        return fit_mean(*data, kind=mean_function, verbose=bool(progress), **kw)[0]
+    from gpfit.amplitude import fit_hyper
+    theta, _ = fit_hyper(*data, verbose=bool(progress), **kw)
     return theta
 
 
@@ -85,22 +112,26 @@ def _merge(frames, on):
 
 
 def process_experiment(x_known, y_known, e_known, resolution, dim_labels, filename, exp_idx, total_exps,
-                       PSO_progress, hyper_samples=None, **pso):
+                       PSO_progress, hyper_samples=None, mean_function=None, **pso):
     """Length scales by PSO, hull grid, GP prediction -> DataFrame (GP_fit.py:20-46). hyper_samples=K
     writes the prediction marginalised over K length-scale samples instead of GP's."""
     if x_known.shape[1] == 0:
         print("  Skipping experiment: no valid data points")
         return None
     full = pso.get("objective") == "marginal_likelihood_full"
+    if mean_function is not None and not full:
+        raise ValueError("mean_function is valid only with len_scale_objective: marginal_likelihood_full")
     if full:
         if hyper_samples is not None:
             raise ValueError("options.yaml: hyper_samples does not combine with len_scale_objective: "
                              "marginal_likelihood_full")
-        ls = _fit_full(x_known, y_known, e_known, PSO_progress, pso)
+        ls = _fit_full(x_known, y_known, e_known, PSO_progress, pso, mean_function)
     else:
         ls = len_scale_opt(x_known, y_known, e_known, PSO_progress, **pso)
     grid = fill_convex_hull(x_known.T, resolution)
-    if full:
+    if full and mean_function is not None:
+        mu, sd = GP_mean(x_known, y_known, e_known, grid.T, ls, mean_function)
+    elif full:
         mu, sd = GP_hyper(x_known, y_known, e_known, grid.T, ls)
     elif hyper_samples is None:
         mu, sd = GP(x_known, y_known, e_known, grid.T, ls)
@@ -159,6 +190,9 @@ def create_GP():
     hyper = _hyper_samples()
     if hyper is not None:
         pso = dict(pso, hyper_samples=hyper)
+    mean_function = _mean_function()
+    if mean_function is not None:
+        pso = dict(pso, mean_function=mean_function)
     nd = len(resolution)
     dim_labels = labels[:nd]
     out_path = Path(out_name) if out_name else Path("GP_results.txt")

@@ -13,7 +13,7 @@ import numpy as np
 
 from gpfit._lib import default_context
 
-__all__ = ["GP", "GP_cov", "GP_draws", "GP_hyper", "GP_loo", "kernel_func"]
+__all__ = ["GP", "GP_cov", "GP_draws", "GP_hyper", "GP_loo", "GP_mean", "kernel_func"]
 
 
 def GP(x_known, y_known, e_known, x_fit, lengths, batch_size=10000):
@@ -109,6 +109,19 @@ def GP_hyper(x_known, y_known, e_known, x_fit, theta):
     if x_fit.ndim != 2 or x_fit.shape[0] != x_known.shape[0]:
         raise ValueError("x_fit must be (d, M) with the same d as x_known")
     return predict_hyper(x_known, y_known, e_known, x_fit, theta)
+
+
+def GP_mean(x_known, y_known, e_known, x_fit, theta, kind="constant"):
+    """GP_hyper() with a polynomial mean function (kind: "constant", "linear" or "quadratic") whose
+    coefficients are integrated out under a flat prior: away from the data the mean tends to the fitted
+    polynomial, not to 0, and sigma includes the share of not knowing the coefficients
+    (gpfit.meanfn.predict_mean, gpf_predict_mean; theta from gpfit.meanfn.fit_mean)."""
+    from gpfit.meanfn import predict_mean
+    x_known = np.asarray(x_known, dtype=np.float64)
+    x_fit = np.asarray(x_fit, dtype=np.float64)
+    if x_fit.ndim != 2 or x_fit.shape[0] != x_known.shape[0]:
+        raise ValueError("x_fit must be (d, M) with the same d as x_known")
+    return predict_mean(x_known, y_known, e_known, x_fit, theta, kind)
 
 
 def kernel_func(x1, x2, l):

@@ -34,6 +34,7 @@
 #include "gpf_lmlgrad.hip"
 #include "gpf_loo.hip"
 #include "gpf_hyperlml.hip"
+#include "gpf_meanfn.hip"
 #include "gpf_probsurf.hip"
 #include "gpf_hull.hip"
 #include "gpf_kmeans.hip"
@@ -131,7 +132,7 @@ double device_bytes(const size_t* bytes, unsigned pinned_mask, int n) {
 }
 
 // The entry points that keep a set
-enum KeptId { KEPT_PRED = 0, KEPT_PCOV, KEPT_PDRAW, KEPT_LIN, KEPT_CON, KEPT_PBATCH, KEPT_DCHOL, KEPT_PSURF, KEPT_N };
+enum KeptId { KEPT_PRED = 0, KEPT_PCOV, KEPT_PDRAW, KEPT_LIN, KEPT_CON, KEPT_PBATCH, KEPT_DCHOL, KEPT_PSURF, KEPT_PMEAN, KEPT_N };
 
 }  // namespace
 
@@ -199,6 +200,13 @@ struct gpf_ctx {
   // gpf_lml_hyper_batch: per particle (a, s), the four results of k_hyper_value, alt and alt / a
   // (Npad doubles each). Its own, like loo: no other call reads or writes it
   Scratch hyp;
+  // the mean function's basis (gpf_set_basis): H zero-padded to [bmpad][Npad], bm rows (0: none);
+  // every gpf_set_data discards it
+  double* d_H = nullptr;
+  int bm = 0, bmpad = 0;
+  // gpf_lml_mean_batch: per particle (a, s), the results of k_mean_small / k_mean_hyper, t, beta, La^-1,
+  // alt, at / a, zr, Z / Zo, Bt and -Bt (MeanBufs). Its own, like hyp
+  Scratch mean;
   // pinned host staging for the per-batch transfers (async DMA, capturable in graphs)
   double* h_ls = nullptr;
   double* h_loss = nullptr;
@@ -335,7 +343,7 @@ static void free_work(gpf_ctx* c) {
   c->d_cflag = nullptr;
   hipFree(c->d_pst);
   c->d_pst = nullptr;
-  for (Scratch* s : {&c->part, &c->cnt, &c->la, &c->pb, &c->pstart, &c->lb, &c->loo, &c->hyp}) s->release();
+  for (Scratch* s : {&c->part, &c->cnt, &c->la, &c->pb, &c->pstart, &c->lb, &c->loo, &c->hyp, &c->mean}) s->release();
   c->d_L = c->d_U = c->d_yb = c->d_s2p = c->d_szp = c->d_ls = c->d_mu = c->d_sd = c->d_loss = nullptr;
   c->d_info = nullptr;
   c->d_hist = nullptr;
@@ -696,6 +704,7 @@ void gpf_close(gpf_ctx* c) {
   harvest(c);
   free_work(c);
   hipFree(c->d_x); hipFree(c->d_y); hipFree(c->d_e);
+  hipFree(c->d_H);
   hipFree(c->d_clk);
   c->gpart.release();
   hipFree(c->d_sig); hipFree(c->d_exp); hipFree(c->d_lo); hipFree(c->d_hi);
@@ -722,6 +731,9 @@ int gpf_set_data(gpf_ctx* c, const double* x, const double* y, const double* e, 
   free_work(c);
   hipFree(c->d_x); hipFree(c->d_y); hipFree(c->d_e);
   c->d_x = c->d_y = c->d_e = nullptr;
+  hipFree(c->d_H);  // the basis belongs to the training points it was evaluated at
+  c->d_H = nullptr;
+  c->bm = c->bmpad = 0;
   if (d != c->d) {  // the search box is per dimension: a new d discards it (gpf_eval_batch asks for a new gpf_set_grid)
     c->h_lo.clear();
     c->h_hi.clear();
@@ -2030,7 +2042,8 @@ int gpf_log_marginal_likelihood(gpf_ctx* c, const double* ls, double* out) {
   return GPF_OK;
 }
 
-// ---- the batched objectives over the chunk workspace: gpf_lml_batch, gpf_loo_batch, gpf_lml_hyper_batch ----
+// ---- the batched objectives over the chunk workspace: gpf_lml_batch, gpf_loo_batch, gpf_lml_hyper_batch,
+// gpf_lml_mean_batch ----
 
 // The flops of W = U^T U on the lower tiles, the same N^3/3 as the factorisation: the sum over the
 // tiles (I, J <= I) of 2 T^3 (nt - I) (k_lml_grad, k_loo_w)
@@ -2062,6 +2075,9 @@ struct Objective {
   std::function<void(int pc, double* partial)> tiles;
   std::function<int(int s, int pc)> fetch;              // the pass's results to the host (hval and the call's own outputs)
   std::function<void(int p, int q, bool bad)> outputs;  // optional: the call's own per-particle outputs
+  // optional: a failure of the call's own in slot q whose factorisation succeeded (from what `fetch`
+  // brought back); it sets c->err and the particle is GPF_NOT_PD like one whose matrix failed
+  std::function<bool(int q)> failed;
 };
 
 // The passes of a batched objective: stage the length scales, factorise, run the call's kernels, finish
@@ -2081,6 +2097,7 @@ static int objective_batch(gpf_ctx* c, const Knobs& knobs, const Objective& o) {
     hg.resize((size_t)o.pass * d);
   }
   int ret = GPF_OK, rc;
+  std::string first_err;
   for (int s = 0; s < o.P; s += o.pass) {
     const int pc = std::min(o.pass, o.P - s);
     for (int q = 0; q < pc; ++q) std::memcpy(c->h_ls + (size_t)q * d, o.rows + (size_t)(s + q) * o.stride, (size_t)d * 8);
@@ -2105,9 +2122,10 @@ static int objective_batch(gpf_ctx* c, const Knobs& knobs, const Objective& o) {
       const int p = s + q;
       const int st = particle_status(c, q);
       if (st == GPF_HIP_ERROR) return st;
-      const bool bad = st != GPF_OK;
+      const bool bad = st != GPF_OK || (o.failed && o.failed(q));
       if (bad && ret == GPF_OK) {
         ret = GPF_NOT_PD;
+        first_err = c->err;
         if (o.bad_idx) *o.bad_idx = p;
       }
       if (o.status) o.status[p] = bad ? GPF_NOT_PD : GPF_OK;
@@ -2117,6 +2135,7 @@ static int objective_batch(gpf_ctx* c, const Knobs& knobs, const Objective& o) {
       if (o.outputs) o.outputs(p, q, bad);
     }
   }
+  if (ret != GPF_OK) c->err = first_err;  // the message of the particle *bad_idx names
   return ret;
 }
 
@@ -2314,6 +2333,335 @@ int gpf_lml_hyper_batch(gpf_ctx* c, const double* th, int P, double* lml, double
     }
   };
   return objective_batch(c, knobs, o);
+}
+
+// ---- the marginalised polynomial mean: gpf_set_basis, gpf_lml_mean_batch, gpf_predict_mean ----
+int gpf_set_basis(gpf_ctx* c, const double* H, int m) {
+  if (!c) return GPF_BAD_ARG;
+  if (c->N <= 0) return bad_arg(c, "gpf_set_basis: call gpf_set_data first");
+  if (!H || m < 1 || m > gpf::MEAN_MAX) return bad_arg(c, "gpf_set_basis: the basis needs 1 to 32 rows");
+  if ((int64_t)m >= c->N) return bad_arg(c, "gpf_set_basis: the basis needs fewer rows than there are points");
+  const int64_t N = c->N, Np = c->Npad;
+  for (int64_t i = 0; i < (int64_t)m * N; ++i)
+    if (!std::isfinite(H[i])) return bad_arg(c, "gpf_set_basis: the basis must be finite");
+  const int mp = (m + 15) / 16 * 16;
+  std::vector<double> hp((size_t)mp * Np, 0.0);
+  for (int r = 0; r < m; ++r) std::memcpy(hp.data() + (size_t)r * Np, H + (size_t)r * N, (size_t)N * 8);
+  hipSetDevice(c->device);
+  GPF_HIP(c, hipStreamSynchronize(c->stream));  // (the last mean call may still read the old basis)
+  hipFree(c->d_H);
+  c->d_H = nullptr;
+  c->bm = c->bmpad = 0;
+  GPF_HIP(c, hipMalloc(&c->d_H, hp.size() * 8));
+  GPF_HIP(c, hipMemcpy(c->d_H, hp.data(), hp.size() * 8, hipMemcpyHostToDevice));
+  c->bm = m;
+  c->bmpad = mp;
+  return GPF_OK;
+}
+
+namespace {
+// The per-particle buffers of a mean call inside one allocation for `pc` slots
+struct MeanBufs {
+  double *as, *out, *t, *beta, *La, *al, *sc, *zr, *Z, *Bt, *nBt;
+  static size_t doubles(size_t pc, size_t Np, size_t mp) {
+    return pc * (2 + gpf::MV_N + 2 * gpf::MEAN_MAX + gpf::MEAN_MAX * gpf::MEAN_MAX + 3 * Np + 3 * Np * mp);
+  }
+  MeanBufs(double* base, size_t pc, size_t Np, size_t mp) {
+    as = base;
+    out = as + pc * 2;
+    t = out + pc * gpf::MV_N;
+    beta = t + pc * gpf::MEAN_MAX;
+    La = beta + pc * gpf::MEAN_MAX;                // k_mean_small's Lai = La^-1, 32 x 32 per slot
+    al = La + pc * gpf::MEAN_MAX * gpf::MEAN_MAX;  // (an even offset: Z's 16-byte loads stay aligned)
+    sc = al + pc * Np;
+    zr = sc + pc * Np;
+    Z = zr + pc * Np;
+    Bt = Z + pc * Np * mp;
+    nBt = Bt + pc * Np * mp;  // -Bt: k_mean_grad's A panel
+  }
+};
+}  // namespace
+
+// Z = U H^T, then k_mean_small, for the first pc slots of the workspace on c->stream
+static int mean_enqueue_small(gpf_ctx* c, int pc, const MeanBufs& b) {
+  const int Np = (int)c->Npad, nt = c->nt, N = (int)c->N, m = c->bm, mp = c->bmpad;
+  const double bytes = 8.0 * T * T * (double)(nt * (nt + 1) / 2) * pc;
+  int rc = launch(c, PC_LOSS, bytes, [&] {
+    if (mp == 16)
+      hipLaunchKernelGGL(gpf::k_mean_nn<1>, dim3(nt, pc), dim3(gpf::DNTH), 0, c->stream, Np, nt, c->d_U, c->d_H, b.Z);
+    else
+      hipLaunchKernelGGL(gpf::k_mean_nn<2>, dim3(nt, pc), dim3(gpf::DNTH), 0, c->stream, Np, nt, c->d_U, c->d_H, b.Z);
+  });
+  if (rc) return rc;
+  // (the partials of Z^T Z wait in Bt's place, nt mp^2 of its 128 nt mp doubles per slot: Bt is formed
+  // after k_mean_small has added them up)
+  return launch(c, PC_LOSS, 0.0, [&] {
+    if (mp == 16) {
+      hipLaunchKernelGGL(gpf::k_mean_gram<16>, dim3(nt, pc), dim3(NTHR), 0, c->stream, Np, nt, m, b.Z, b.Bt);
+      hipLaunchKernelGGL(gpf::k_mean_small<16>, dim3(pc), dim3(NTHR), 0, c->stream, N, Np, nt, m, b.Z, b.Bt, c->d_yb, c->d_L,
+                         b.as, b.out, b.t, b.beta, b.La, b.zr);
+    } else {
+      hipLaunchKernelGGL(gpf::k_mean_gram<32>, dim3(nt, pc), dim3(NTHR), 0, c->stream, Np, nt, m, b.Z, b.Bt);
+      hipLaunchKernelGGL(gpf::k_mean_small<32>, dim3(pc), dim3(NTHR), 0, c->stream, N, Np, nt, m, b.Z, b.Bt, c->d_yb, c->d_L,
+                         b.as, b.out, b.t, b.beta, b.La, b.zr);
+    }
+  });
+}
+
+// Zo^T U for the first pc slots into out[slot * ostride + row * rs + column * cs], and its negative
+// into nout (nullable) likewise (k_mean_tn)
+static int mean_enqueue_tn(gpf_ctx* c, int pc, const MeanBufs& b, double* out, double* nout, size_t ostride, int rs, int cs) {
+  const int Np = (int)c->Npad, nt = c->nt;
+  const double bytes = 8.0 * T * T * (double)(nt * (nt + 1) / 2) * pc;
+  return launch(c, PC_LOSS, bytes, [&] {
+    if (c->bmpad == 16)
+      hipLaunchKernelGGL(gpf::k_mean_tn<1>, dim3(nt, pc), dim3(gpf::DNTH), 0, c->stream, Np, nt, c->d_U, b.Z, out, nout, ostride,
+                         rs, cs);
+    else
+      hipLaunchKernelGGL(gpf::k_mean_tn<2>, dim3(nt, pc), dim3(gpf::DNTH), 0, c->stream, Np, nt, c->d_U, b.Z, out, nout, ostride,
+                         rs, cs);
+  });
+}
+
+int gpf_lml_mean_batch(gpf_ctx* c, const double* th, int P, double* lml, double* grad, double* beta, double* qout,
+                       int* status, int* bad_idx) {
+  if (!c) return GPF_BAD_ARG;
+  if (bad_idx) *bad_idx = -1;
+  if (P < 0 || (P > 0 && (!th || !lml))) return bad_arg(c, "gpf_lml_mean_batch: bad arguments");
+  if (c->N <= 0) return bad_arg(c, "gpf_lml_mean_batch: call gpf_set_data first");
+  if (c->bm <= 0) return bad_arg(c, "gpf_lml_mean_batch: no basis for this data: call gpf_set_basis after gpf_set_data");
+  const int d = c->d, nt = c->nt, dh = d + 2, m = c->bm, mp = c->bmpad;
+  std::vector<double> has((size_t)P * 2), hr((size_t)P);
+  for (int p = 0; p < P; ++p) {
+    const double* row = th + (size_t)p * dh;
+    if (int rl = check_ls(c, "gpf_lml_mean_batch", row, (size_t)d)) return rl;
+    const double a = row[d], s = row[d + 1];
+    if (!(a > 0.0) || !std::isfinite(a) || !(s > 0.0) || !std::isfinite(s))
+      return bad_arg(c, "gpf_lml_mean_batch: amplitude and noise scale must be finite and > 0");
+    const double q = s / a, r = q * q;
+    if (!(r > 0.0) || !std::isfinite(r))
+      return bad_arg(c, "gpf_lml_mean_batch: the noise factor (s / a)^2 must be finite and > 0");
+    has[(size_t)2 * p] = a;
+    has[(size_t)2 * p + 1] = s;
+    hr[p] = r;
+  }
+  if (P == 0) return GPF_OK;
+  hipSetDevice(c->device);
+  const int64_t N = c->N, Np = c->Npad;
+  const Knobs knobs = Knobs::from_env();
+  int rc = ensure_work(c, P, knobs);
+  if (rc) return rc;
+  const int pcm = std::min(c->cap, P);
+  // (synchronised regrow: the previous call's kernels may still be reading it)
+  if ((rc = c->mean.grow(c, MeanBufs::doubles((size_t)pcm, (size_t)Np, (size_t)mp) * 8, false, true))) return rc;
+  const MeanBufs b(c->mean.as<double>(), (size_t)pcm, (size_t)Np, (size_t)mp);
+  const int ntile = nt * (nt + 1) / 2;
+  std::vector<double> ho((size_t)pcm * gpf::MV_N), hb((size_t)pcm * gpf::MEAN_MAX);
+  Objective o;
+  o.rows = th, o.stride = dh, o.P = P, o.pass = pcm, o.nfac = c->d_nfac;
+  o.value = lml, o.hval = ho.data() + gpf::MV_LML, o.hstride = gpf::MV_N;
+  // k_mean_grad: k_lml_grad's chain and mpad more of depth on every lower tile
+  o.grad = grad, o.gstride = dh, o.grad_flops = tri_gemm_flops(nt) + 2.0 * (double)T * T * mp * (double)ntile;
+  o.status = status, o.bad_idx = bad_idx;
+  o.upload = [&](int s, int pc) -> int {
+    GPF_HIP(c, hipMemcpyAsync(c->d_nfac, hr.data() + s, (size_t)pc * 8, hipMemcpyHostToDevice, c->stream));
+    GPF_HIP(c, hipMemcpyAsync(b.as, has.data() + (size_t)2 * s, (size_t)pc * 2 * 8, hipMemcpyHostToDevice, c->stream));
+    return GPF_OK;
+  };
+  o.enqueue = [&](int pc) -> int {
+    if (int r1 = mean_enqueue_small(c, pc, b)) return r1;
+    if (!grad) return GPF_OK;
+    // Bt = Zo^T U, then alt, at / a and the derivatives in a and s
+    if (int r2 = mean_enqueue_tn(c, pc, b, b.Bt, b.nBt, (size_t)mp * Np, (int)Np, 1)) return r2;
+    return launch(c, PC_LOSS, 0.0, [&] {
+      hipLaunchKernelGGL(gpf::k_alpha_batch, dim3((unsigned)((N + NTHR - 1) / NTHR), pc), dim3(NTHR), 0, c->stream, (int)N,
+                         (int)Np, nt, c->d_szp, b.al);
+      hipLaunchKernelGGL(gpf::k_mean_hyper, dim3(pc), dim3(NTHR), 0, c->stream, (int)N, (int)Np, nt, m, mp, c->d_e, b.al,
+                         c->d_s2p, b.Bt, b.t, b.as, b.out, b.sc);
+    });
+  };
+  o.tiles = [&](int pc, double* partial) {
+    hipLaunchKernelGGL(gpf::k_mean_grad, dim3((unsigned)ntile, pc), dim3(gpf::Geo<T>::NTH), 0, c->stream, (int)N, (int)Np, nt, d,
+                       mp, c->d_x, c->d_ls, c->d_U, b.Bt, b.nBt, b.sc, partial);
+  };
+  o.fetch = [&](int, int pc) -> int {
+    GPF_HIP(c, hipMemcpyAsync(ho.data(), b.out, (size_t)pc * gpf::MV_N * 8, hipMemcpyDeviceToHost, c->stream));
+    if (beta) GPF_HIP(c, hipMemcpyAsync(hb.data(), b.beta, (size_t)pc * gpf::MEAN_MAX * 8, hipMemcpyDeviceToHost, c->stream));
+    return GPF_OK;
+  };
+  o.failed = [&](int q) {
+    if (ho[(size_t)q * gpf::MV_N + gpf::MV_BAD] == 0.0) return false;
+    c->err = "H Kt^-1 H^T is not positive definite (the basis is rank-deficient for this particle)";
+    return true;
+  };
+  o.outputs = [&](int p, int q, bool bad) {
+    const double* r = ho.data() + (size_t)q * gpf::MV_N;
+    if (qout) qout[p] = bad ? NAN : r[gpf::MV_Q];
+    if (beta)
+      for (int k = 0; k < m; ++k) beta[(size_t)p * m + k] = bad ? NAN : hb[(size_t)q * gpf::MEAN_MAX + k];
+    if (grad) {
+      grad[(size_t)p * dh + d] = bad ? NAN : r[gpf::MV_DA];
+      grad[(size_t)p * dh + d + 1] = bad ? NAN : r[gpf::MV_DS];
+    }
+  };
+  return objective_batch(c, knobs, o);
+}
+
+// gpf_predict_mean's kept buffers: gpf_predict's, then its own
+enum PmeanBuf {
+  PMEAN_HF = PRED_NBUF,  // the basis at the chunk's query points, mpad x Cp
+  PMEAN_W,               // the single particle's MeanBufs
+  PMEAN_BT,              // Bt^T zero-padded to a 128-wide operand, Np x 128
+  PMEAN_KB,              // K_s^T Bt^T of the chunk, Cp x 128
+  PMEAN_PART,            // k_con_tn's partial tiles
+  PMEAN_HH,              // pinned staging of the basis
+  PMEAN_NBUF
+};
+constexpr unsigned PMEAN_PINNED = PRED_PINNED | 1u << PMEAN_HH;
+// depth tiles per piece of K_s^T Bt^T: a constant, so that the pieces (and with them every bit of the
+// result) do not depend on the query chunk
+constexpr int PMEAN_PER = 4;
+
+static SetPlan pmean_plan(const gpf_ctx* c, int64_t Cp) {
+  SetPlan p = pred_plan(c, Cp);
+  const size_t C = (size_t)Cp, Np = (size_t)c->Npad;
+  p.bytes[PMEAN_HF] = p.bytes[PMEAN_HH] = (size_t)c->bmpad * C * 8;
+  p.bytes[PMEAN_W] = MeanBufs::doubles(1, Np, (size_t)c->bmpad) * 8;
+  p.bytes[PMEAN_BT] = Np * T * 8;
+  p.bytes[PMEAN_KB] = C * T * 8;
+  p.bytes[PMEAN_PART] = (size_t)((c->nt + PMEAN_PER - 1) / PMEAN_PER) * (C / T) * gpf::LIN_TT * 8;
+  return p;
+}
+
+int gpf_predict_mean(gpf_ctx* c, const double* ls, const double* xfit, const double* hfit, int64_t M, int64_t batch,
+                     double* mu, double* sd, double* beta, double* bcov) {
+  if (!c) return GPF_BAD_ARG;
+  if (c->N <= 0) return bad_arg(c, "gpf_predict_mean: call gpf_set_data first");
+  if (c->bm <= 0) return bad_arg(c, "gpf_predict_mean: no basis for this data: call gpf_set_basis after gpf_set_data");
+  if (M < 0 || (M > 0 && (!xfit || !hfit || !mu || !sd)) || !ls) return bad_arg(c, "gpf_predict_mean: bad arguments");
+  if (int rl = check_ls(c, "gpf_predict_mean", ls, (size_t)c->d)) return rl;
+  if (M == 0) return GPF_OK;
+  hipSetDevice(c->device);
+  if (c->K <= 0) c->K = 2;  // (as gpf_predict: the objective grid is not needed)
+  const Knobs knobs = Knobs::from_env();
+  if (int rw = ensure_work(c, 1, knobs)) return rw;
+  KeptSet& ks = c->kept[KEPT_PMEAN];
+  const int64_t Np = c->Npad;
+  const int nt = c->nt, m = c->bm, mp = c->bmpad;
+  const int pieces = (nt + PMEAN_PER - 1) / PMEAN_PER;
+  int64_t chunk = std::min<int64_t>(std::max<int64_t>(std::max<int64_t>(batch, 1), 16384), M);
+  int64_t Cp = ((chunk + T - 1) / T) * T;
+  SetPlan p = pmean_plan(c, Cp);
+  if (!ks.fits(p.bytes, PMEAN_NBUF)) {
+    Budget bg;
+    if (int rb = half_free(c, nullptr, &bg)) return rb;
+    const int64_t per_col = (Np + 2 * nt + T + mp + (int64_t)pieces * T) * 8;
+    const int64_t maxcols = std::max<int64_t>(T, (int64_t)(bg.half / (double)per_col));
+    chunk = std::min<int64_t>(chunk, maxcols);
+    Cp = ((chunk + T - 1) / T) * T;
+    p = pmean_plan(c, Cp);
+    if (!ks.fits(p.bytes, PMEAN_NBUF))
+      if (int rg = ks.regrow(c, p.bytes, PMEAN_PINNED, PMEAN_NBUF)) return rg;
+  }
+  double *d_xf = ks.as(PRED_XF), *d_ks = ks.as(PRED_KS), *d_vsq = ks.as(PRED_VSQ), *d_vz = ks.as(PRED_VZ);
+  double *d_mu = ks.as(PRED_MU), *d_sd = ks.as(PRED_SD), *hx = ks.as(PRED_HX), *hout = ks.as(PRED_HOUT);
+  double *d_hf = ks.as(PMEAN_HF), *d_bt = ks.as(PMEAN_BT), *d_kb = ks.as(PMEAN_KB), *d_part = ks.as(PMEAN_PART);
+  double* hh = ks.as(PMEAN_HH);
+  const MeanBufs b(ks.as(PMEAN_W), 1, (size_t)Np, (size_t)mp);
+  auto stage_chunk = [&](int64_t s0, int64_t mq) -> int {
+    for (int k = 0; k < c->d; ++k) std::memcpy(hx + (size_t)k * Cp, xfit + (size_t)k * M + s0, (size_t)mq * 8);
+    for (int r = 0; r < m; ++r) std::memcpy(hh + (size_t)r * Cp, hfit + (size_t)r * M + s0, (size_t)mq * 8);
+    GPF_HIP(c, hipMemcpyAsync(d_xf, hx, (size_t)c->d * Cp * 8, hipMemcpyHostToDevice, c->stream));
+    GPF_HIP(c, hipMemcpyAsync(d_hf, hh, (size_t)m * Cp * 8, hipMemcpyHostToDevice, c->stream));
+    return GPF_OK;
+  };
+  std::memcpy(c->h_ls, ls, (size_t)c->d * 8);
+  GPF_HIP(c, hipMemcpyAsync(c->d_ls, c->h_ls, (size_t)c->d * 8, hipMemcpyHostToDevice, c->stream));
+  int rc = stage_chunk(0, std::min<int64_t>(chunk, M));
+  if (rc) return rc;
+  const double ones[2] = {1.0, 1.0};  // the unit model: (a, s) go through the data (gpfit.amplitude.scaled_data)
+  GPF_HIP(c, hipMemcpyAsync(b.as, ones, 16, hipMemcpyHostToDevice, c->stream));
+  GPF_HIP(c, hipMemsetAsync(d_bt, 0, (size_t)Np * T * 8, c->stream));
+  rc = factor_single_async(c, nullptr, nullptr, knobs);
+  if (rc) return rc;
+  // Zo, t, beta, La and zr of slot 0, then Bt^T into the 128-wide operand
+  if ((rc = mean_enqueue_small(c, 1, b))) return rc;
+  if ((rc = mean_enqueue_tn(c, 1, b, d_bt, nullptr, 0, 1, T))) return rc;
+  std::vector<double> hsmall(gpf::MV_N + 2 * gpf::MEAN_MAX);  // out | t | beta of slot 0
+  for (int64_t s = 0; s < M && rc == GPF_OK; s += chunk) {
+    const int64_t mq = std::min<int64_t>(chunk, M - s);
+    const int nqt = (int)((mq + T - 1) / T);
+    const int Cm = nqt * T;
+    if (s > 0) {
+      if (hipStreamSynchronize(c->stream) != hipSuccess) {  // the staging buffers are reused
+        rc = GPF_HIP_ERROR;
+        break;
+      }
+      if ((rc = stage_chunk(s, mq))) break;
+    }
+    rc = launch(c, PC_PREDK, 8.0 * Np * Cm, [&] {
+      gpf::launch_cross_cov(c->stream, (int)c->N, (int)mq, (int)Np, Cm, c->d, c->d_x, (int)c->N, d_xf, (int)Cp, c->d_ls,
+                            d_ks, (int64_t)Cp);
+    });
+    if (rc) break;
+    // K_s^T at and sum v^2: gpf_predict's kernel with zr in z's place
+    const double vflops = 2.0 * T * T * (double)Cm * ((double)nt * (nt + 1) / 2) - (double)T * T * Cm * nt;
+    rc = launch(c, PC_PRED, vflops, [&] {
+      hipLaunchKernelGGL(gpf::k_predict_vsq, dim3(nqt, nt), dim3(gpf::Geo<T>::NTH), 0, c->stream, (int)Np, c->d_U, d_ks,
+                         (int)Cp, d_vsq, b.zr, d_vz, 0);
+    });
+    if (rc) break;
+    // K_s^T Bt^T over fixed depth pieces, added in piece order
+    rc = launch(c, PC_PRED, 2.0 * (double)Np * Cm * T, [&] {
+      hipLaunchKernelGGL(gpf::k_con_tn, dim3((unsigned)nqt, (unsigned)pieces), dim3(gpf::Geo<T>::NTH), 0, c->stream, 1, nt,
+                         PMEAN_PER, 0, d_ks, (int)Cp, d_bt, T, d_part);
+      hipLaunchKernelGGL(gpf::k_lin_reduce, dim3((unsigned)nqt, 8), dim3(NTHR), 0, c->stream, 1, 0, pieces, d_part,
+                         (const double*)nullptr, 1.0, d_kb, (int64_t)T);
+    });
+    if (rc) break;
+    rc = launch(c, PC_LOSS, 0.0, [&] {
+      hipLaunchKernelGGL(gpf::k_mean_out, dim3((unsigned)((mq + NTHR - 1) / NTHR)), dim3(NTHR), 0, c->stream, nt, (int)mq, m, d_vz,
+                         (int)Cp, d_vsq, d_hf, d_kb, T, b.La, b.beta, d_mu, d_sd);
+    });
+    if (rc) break;
+    if (hipMemcpyAsync(hout, d_mu, (size_t)mq * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipMemcpyAsync(hout + Cp, d_sd, (size_t)mq * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        (s == 0 && hipMemcpyAsync(hsmall.data(), b.out, hsmall.size() * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+        hipStreamSynchronize(c->stream) != hipSuccess) {
+      rc = GPF_HIP_ERROR;
+      c->err = "gpf_predict_mean: copy back failed";
+      break;
+    }
+    if (s == 0) {  // the factorisation's status and At's, before anything reaches the caller's buffers
+      rc = particle_status(c, 0);
+      if (!rc && hsmall[gpf::MV_BAD] != 0.0) {
+        c->err = "H Kt^-1 H^T is not positive definite (the basis is rank-deficient at these length scales)";
+        rc = GPF_NOT_PD;
+      }
+      if (rc) break;
+    }
+    std::memcpy(mu + s, hout, (size_t)mq * 8);
+    std::memcpy(sd + s, hout + Cp, (size_t)mq * 8);
+  }
+  hipStreamSynchronize(c->stream);
+  if (c->prof) harvest(c);
+  if (rc == GPF_OK) {
+    // out | t | beta lie behind one another in MeanBufs: beta from the copy of chunk 0
+    const double* hbeta = hsmall.data() + gpf::MV_N + gpf::MEAN_MAX;
+    if (beta) std::memcpy(beta, hbeta, (size_t)m * 8);
+    if (bcov) {  // cov(beta) = At^-1 = Lai^T Lai from k_mean_small's Lai = La^-1 (m <= 32: on the host)
+      std::vector<double> inv((size_t)gpf::MEAN_MAX * gpf::MEAN_MAX);
+      GPF_HIP(c, hipMemcpy(inv.data(), b.La, inv.size() * 8, hipMemcpyDeviceToHost));
+      for (int i = 0; i < m; ++i)
+        for (int j = 0; j < m; ++j) {
+          double v = 0.0;
+          for (int k = std::max(i, j); k < m; ++k) v += inv[(size_t)k * gpf::MEAN_MAX + i] * inv[(size_t)k * gpf::MEAN_MAX + j];
+          bcov[(size_t)i * m + j] = v;
+        }
+    }
+  }
+  ks.trim(knobs);
+  return rc;
 }
 
 // ---- gpf_predict_batch: prediction for a batch of length-scale samples and their mixture ----

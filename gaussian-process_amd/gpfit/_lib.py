@@ -20,6 +20,7 @@ GPF_OK, GPF_NOT_PD, GPF_HIP_ERROR, GPF_BAD_ARG = 0, 1, 2, 3
 GPF_COMM_RCCL, GPF_COMM_HOST = 1, 2
 GPF_OP_SUM, GPF_OP_MAX = 0, 1
 ABI_VERSION = 2
+MEAN_MAX = 32  # rows of a mean function's basis at most (gpf_set_basis)
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int)
@@ -48,6 +49,9 @@ SIGNATURES = {
     "gpf_lml_batch": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _dp, _dp, _ip, _ip]),
     "gpf_loo_batch": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _dp, _dp, _dp, _dp, _ip, _ip]),
     "gpf_lml_hyper_batch": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _dp, _dp, _dp, _ip, _ip]),
+    "gpf_set_basis": (ctypes.c_int, [_vp, _dp, ctypes.c_int]),
+    "gpf_lml_mean_batch": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _dp, _dp, _dp, _dp, _ip, _ip]),
+    "gpf_predict_mean": (ctypes.c_int, [_vp, _dp, _dp, _dp, ctypes.c_int64, ctypes.c_int64, _dp, _dp, _dp, _dp]),
     "gpf_predict_batch": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _dp, _dp, ctypes.c_int64, ctypes.c_int64,
                                          _dp, _dp, _dp, _dp, _ip]),
     "gpf_predict_batch_plan": (ctypes.c_int, [ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_double,
@@ -209,6 +213,7 @@ class Context:
         self._h = h
         self.N = 0
         self.d = 0
+        self.m = 0  # rows of the mean function's basis (set_basis), 0: none
         self._data_key = None
         self._grid_key = None
 
@@ -250,6 +255,7 @@ class Context:
         self.N, self.d = n, d
         self._data_key = key
         self._grid_key = None
+        self.m = 0  # gpf_set_data discards the mean function's basis
 
     def set_grid(self, sigma_vals, expected, lo, hi):
         s, ex = _f64(sigma_vals), _f64(expected)
@@ -534,6 +540,91 @@ class Context:
         if rc != GPF_NOT_PD or strict:
             self._check(rc, "gpf_lml_hyper_batch", bad)
         return (lml, g, q) if want_q else (lml, g)
+
+    def set_basis(self, H):
+        """The mean function's basis at the training points, H (m, N), 1 <= m <= 32, m < N, finite, full
+        row rank (gpf_set_basis; gpfit.meanfn.basis builds the polynomial ones). Every set_data with
+        new data discards it."""
+        H = _f64(H)
+        if H.ndim == 1:
+            H = H.reshape(1, -1)
+        if not self.N:
+            raise ValueError("set_basis: call set_data first")
+        if H.ndim != 2 or H.shape[1] != self.N:
+            raise ValueError(f"set_basis: H must be (m, {self.N}), the basis at the training points")
+        m = H.shape[0]
+        if not 1 <= m <= MEAN_MAX:
+            raise ValueError(f"set_basis: the basis needs 1 to {MEAN_MAX} rows, got {m}")
+        if m >= self.N:
+            raise ValueError(f"set_basis: the basis needs fewer rows than there are points ({m} >= {self.N})")
+        if not np.all(np.isfinite(H)):
+            raise ValueError("set_basis: the basis must be finite")
+        if np.linalg.matrix_rank(H) < m:
+            raise ValueError("set_basis: H is rank-deficient (its rows must be linearly independent)")
+        self._check(self.lib.gpf_set_basis(self._h, _ptr(H), m), "gpf_set_basis")
+        self.m = m
+
+    def lml_mean_batch(self, theta, grad=True, strict=True, want_q=False, want_beta=False):
+        """lml_hyper_batch with the polynomial mean of set_basis integrated out under a flat prior: the
+        restricted log marginal likelihood of every row (l_1 .. l_d, a, s) of theta (P, d + 2) and,
+        with grad, its gradient in all d + 2 (gpf_lml_mean_batch): (lml (P,), grad (P, d + 2) or None),
+        then with want_q the residual's Q' (P,) (for fixed l and s / a the best amplitude is
+        sqrt(Q' / (N - m))) and with want_beta the coefficients beta (P, m). A particle whose
+        covariance, or whose H Kt^-1 H^T, is not positive definite raises LinAlgError with .particle
+        set (strict), or gets -inf and NaN rows while the others are computed (strict=False)."""
+        th = _f64(theta)
+        if th.ndim == 1:
+            th = th.reshape(1, -1)
+        n = th.shape[0]
+        if th.ndim != 2 or th.shape[1] < 3 or (self.d and th.shape[1] != self.d + 2):
+            raise ValueError(f"theta must be (P, {self.d + 2}): the length scales, then a and s" if self.d
+                             else "theta must be (P, d + 2): the length scales, then a and s")
+        if self.N and not self.m:
+            raise ValueError("lml_mean_batch: no basis for this data: call set_basis after set_data")
+        lml = np.empty(n)
+        g = np.empty(th.shape) if grad else None
+        q = np.empty(n) if want_q else None
+        beta = np.empty((n, self.m)) if want_beta else None
+        status = np.zeros(n, dtype=np.int32)
+        bad = ctypes.c_int(-1)
+        rc = self.lib.gpf_lml_mean_batch(self._h, _ptr(th), n, _ptr(lml), _ptr(g) if grad else None,
+                                         _ptr(beta) if want_beta else None, _ptr(q) if want_q else None,
+                                         status.ctypes.data_as(_ip), ctypes.byref(bad))
+        if rc != GPF_NOT_PD or strict:
+            self._check(rc, "gpf_lml_mean_batch", bad)
+        out = (lml, g)
+        if want_q:
+            out += (q,)
+        if want_beta:
+            out += (beta,)
+        return out
+
+    def predict_mean(self, lengths, x_fit, h_fit, batch_size=10000, want_beta=False):
+        """predict with the mean function of set_basis (gpf_predict_mean, the unit model a = s = 1):
+        (mu (M,), sd (M,)) at x_fit (d, M) with h_fit (m, M) the basis there; sd includes the share of
+        not knowing the coefficients. With want_beta also (beta (m,), cov(beta) (m, m))."""
+        ls = _f64(lengths).reshape(-1)
+        xf, hf = _f64(x_fit), _f64(h_fit)
+        if xf.ndim != 2:
+            raise ValueError("x_fit must be (d, M)")
+        if self.d and (xf.shape[0] != self.d or ls.shape[0] != self.d):
+            raise ValueError(f"x_fit must be ({self.d}, M) and lengths ({self.d},)")
+        if self.N and not self.m:
+            raise ValueError("predict_mean: no basis for this data: call set_basis after set_data")
+        if hf.ndim == 1:
+            hf = hf.reshape(1, -1)
+        mq = xf.shape[1]
+        if hf.ndim != 2 or hf.shape != (self.m, mq):
+            raise ValueError(f"h_fit must be ({self.m}, {mq}): the basis at the query points")
+        if not np.all(np.isfinite(hf)):
+            raise ValueError("predict_mean: h_fit must be finite")
+        mu, sd = np.empty(mq), np.empty(mq)
+        beta = np.empty(self.m) if want_beta else None
+        bcov = np.empty((self.m, self.m)) if want_beta else None
+        self._check(self.lib.gpf_predict_mean(self._h, _ptr(ls), _ptr(xf), _ptr(hf), mq, int(batch_size), _ptr(mu),
+                                              _ptr(sd), _ptr(beta) if want_beta else None,
+                                              _ptr(bcov) if want_beta else None), "gpf_predict_mean")
+        return (mu, sd, beta, bcov) if want_beta else (mu, sd)
 
     def loo_batch(self, positions, grad=True, points=False, strict=True):
         """Leave-one-out log predictive density of every row of positions (P, d) and, with grad, its

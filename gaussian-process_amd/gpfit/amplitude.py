@@ -19,7 +19,7 @@ Nothing downstream needs a kernel of its own: the model with (a, s) on (x, y, e)
 (x, y / a, e s / a) with mu a, sd a and cov a^2 (``scaled_data``, ``predict_hyper``).
 
 Not built: per-particle (a, s) in gpf_predict_batch and gpfit.hyper.sample_hyper, leave-one-out with
-(a, s), a mean function.
+(a, s). (A mean function: gpfit.meanfn, which shares this module's two-stage driver.)
 """
 from __future__ import annotations
 
@@ -86,24 +86,14 @@ def _value_and_q(value_and_grad, theta, n, counts):
     return lml, a * a * (n + a * g[:, -2] + s * g[:, -1])
 
 
-def fit_hyper(x, y, e, *, num_starts=NUM_STARTS, num_polish=NUM_POLISH, max_points=MAX_POINTS, seed=None,
-              value_and_grad=None, ctx=None, verbose=True):
-    """theta = (l_1 .. l_d, a, s) that maximises the log marginal likelihood: (theta (d + 2,), info).
-
-    fit_lml's signature and semantics. ``value_and_grad(theta (P, d + 2)) -> (lml (P,), grad (P, d + 2))``
-    injects an evaluator (the CPU tests); the default is gpf_lml_hyper_batch on this process's GPU. A
-    point whose covariance is not positive definite is a losing point, never an error.
-
-      stage 1  ``num_starts`` centred-Latin-hypercube starts in (log l in fit_lml's box, log(s/a) in
-               [log 0.1, log 10]), scored in one batched value call at a = 1; each gets its best
-               amplitude a = sqrt(Q / N) (kept inside stage 2's box) and the value there, in closed form;
-      stage 2  the ``num_polish`` best polished by L-BFGS-B in (log l, log a, log s); a in
-               [1e-3, 1e3] std(y), s in [1e-2, 1e2].
-
-    info: "lml" (at theta), "evals", "grad_evals", "box" (lower, upper: d + 2 each), "starts"
-    (theta (num_starts, d + 2), lml) and "polished" (one dict per polished start: start, x, lml,
-    start_lml, nfev, nit, message).
-    """
+def _fit_theta(x, y, e, *, who, lost, pin, setup, done_msg, num_starts, num_polish, max_points, seed, value_and_grad,
+               ctx, verbose):
+    """The two-stage driver behind fit_hyper and gpfit.meanfn.fit_mean. ``lost``: the degrees of freedom
+    a marginalised mean takes (m; 0 for fit_hyper), so the best amplitude of a start is
+    sqrt(Q / (N - lost)). ``setup(ctx or None, x, y, e)`` (optional) is called with the prepared points
+    once the data are on the device and returns the evaluator (fit_mean sets its basis there); without
+    it the evaluator is the injected one or gpf_lml_hyper_batch. ``pin``: a = s = 1, only the length
+    scales are fitted (the starts in the length-scale box, stage 2 in log l)."""
     x = np.asarray(x, dtype=np.float64)
     y = np.asarray(y, dtype=np.float64)
     e = np.asarray(e, dtype=np.float64)
@@ -114,22 +104,43 @@ def fit_hyper(x, y, e, *, num_starts=NUM_STARTS, num_polish=NUM_POLISH, max_poin
                                           ctx=None if injected else ctx)
     lower = np.maximum(lower, LOWER_FRACTION * upper)
     if not np.all(upper > lower):
-        raise ValueError("fit_hyper: the search box is empty (a coordinate has no spread)")
+        raise ValueError(f"{who}: the search box is empty (a coordinate has no spread)")
     scale = float(np.std(y))
     if not (np.isfinite(scale) and scale > 0):
-        raise ValueError("fit_hyper: y has no spread")
+        raise ValueError(f"{who}: y has no spread")
     if injected:
         comm = default_comm()
+        if setup is not None:
+            value_and_grad = setup(None, x, y, e)
     else:
         ctx.set_data(x, y, e)
-        value_and_grad = _device_evaluator(ctx)
+        value_and_grad = setup(ctx, x, y, e) if setup is not None else _device_evaluator(ctx)
         comm = default_comm(ctx)
     seed = share_seed(seed, comm)
-    d, n = x.shape[0], y.reshape(-1).shape[0]
+    d, n = x.shape[0], y.reshape(-1).shape[0] - int(lost)
+    if n < 1:
+        raise ValueError(f"{who}: the mean function needs fewer coefficients than there are points")
     counts = {"evals": 0, "grad_evals": 0}
+    if pin:
+        lower = np.concatenate([lower, [1.0, 1.0]])
+        upper = np.concatenate([upper, [1.0, 1.0]])
+        ls = centred_lhs(lower[:d], upper[:d], int(num_starts), seed)
+        starts = np.column_stack([ls, np.ones(len(ls)), np.ones(len(ls))])
+        start_lml, _ = _call(value_and_grad, starts, False)
+        counts["evals"] += starts.shape[0]
+        start_lml = np.where(np.isfinite(start_lml), start_lml, -np.inf)
+        order = np.argsort(-start_lml, kind="stable")[:max(1, int(num_polish))]
+
+        def lengths_only(pos, grad=True):
+            th = np.column_stack([pos, np.ones(len(pos)), np.ones(len(pos))])
+            lml, g = _call(value_and_grad, th, grad)
+            return lml, (g[:, :d] if grad else None)
+        polished = polish_log(lengths_only, starts[:, :d], start_lml, order, lower[:d], upper[:d], "lml", counts)
+        for r in polished:
+            r["start"], r["x"] = np.append(r["start"], [1.0, 1.0]), np.append(r["x"], [1.0, 1.0])
+        return _fit_result(polished, counts, lower, upper, starts, start_lml, d, done_msg, verbose)
     lower = np.concatenate([lower, [A_BOX[0] * scale, S_BOX[0]]])
     upper = np.concatenate([upper, [A_BOX[1] * scale, S_BOX[1]]])
-
     # stage 1: (l, s/a) starts in one batched call at a = 1, then the best amplitude of each
     u = np.exp(centred_lhs(np.log(np.append(lower[:d], RATIO_BOX[0])), np.log(np.append(upper[:d], RATIO_BOX[1])),
                            int(num_starts), seed))
@@ -149,9 +160,13 @@ def fit_hyper(x, y, e, *, num_starts=NUM_STARTS, num_polish=NUM_POLISH, max_poin
 
     # stage 2: L-BFGS-B on -LML in t = log theta
     polished = polish_log(value_and_grad, starts, start_lml, order, lower, upper, "lml", counts)
+    return _fit_result(polished, counts, lower, upper, starts, start_lml, d, done_msg, verbose)
+
+
+def _fit_result(polished, counts, lower, upper, starts, start_lml, d, done_msg, verbose):
     best = max(polished, key=lambda r: r["lml"])
     if verbose:
-        print("Marginal-likelihood fit of length scales, amplitude and noise scale completed.")
+        print(done_msg)
         print("Optimal length scale found:")
         print(best["x"][:d])
         print("Amplitude and noise scale:")
@@ -161,3 +176,27 @@ def fit_hyper(x, y, e, *, num_starts=NUM_STARTS, num_polish=NUM_POLISH, max_poin
     info = {"lml": best["lml"], "evals": counts["evals"], "grad_evals": counts["grad_evals"],
             "box": (lower, upper), "starts": (starts, start_lml), "polished": polished}
     return best["x"].copy(), info
+
+
+def fit_hyper(x, y, e, *, num_starts=NUM_STARTS, num_polish=NUM_POLISH, max_points=MAX_POINTS, seed=None,
+              value_and_grad=None, ctx=None, verbose=True):
+    """theta = (l_1 .. l_d, a, s) that maximises the log marginal likelihood: (theta (d + 2,), info).
+
+    fit_lml's signature and semantics. ``value_and_grad(theta (P, d + 2)) -> (lml (P,), grad (P, d + 2))``
+    injects an evaluator (the CPU tests); the default is gpf_lml_hyper_batch on this process's GPU. A
+    point whose covariance is not positive definite is a losing point, never an error.
+
+      stage 1  ``num_starts`` centred-Latin-hypercube starts in (log l in fit_lml's box, log(s/a) in
+               [log 0.1, log 10]), scored in one batched value call at a = 1; each gets its best
+               amplitude a = sqrt(Q / N) (kept inside stage 2's box) and the value there, in closed form;
+      stage 2  the ``num_polish`` best polished by L-BFGS-B in (log l, log a, log s); a in
+               [1e-3, 1e3] std(y), s in [1e-2, 1e2].
+
+    info: "lml" (at theta), "evals", "grad_evals", "box" (lower, upper: d + 2 each), "starts"
+    (theta (num_starts, d + 2), lml) and "polished" (one dict per polished start: start, x, lml,
+    start_lml, nfev, nit, message).
+    """
+    return _fit_theta(x, y, e, who="fit_hyper", lost=0, pin=False, setup=None,
+                      done_msg="Marginal-likelihood fit of length scales, amplitude and noise scale completed.",
+                      num_starts=num_starts, num_polish=num_polish, max_points=max_points, seed=seed,
+                      value_and_grad=value_and_grad, ctx=ctx, verbose=verbose)

@@ -301,9 +301,58 @@ int gpf_loo_batch(gpf_ctx* ctx, const double* ls_Pd, int P, double* lpd_P, doubl
  * atomics), and lml and q do not depend on whether the gradient is asked for. The call keeps its own
  * buffers: it changes no bit of any other call.
  * Not built: per-particle (a, s) in gpf_predict_batch and in the length-scale sampler, leave-one-out
- * with (a, s), a mean function. */
+ * with (a, s). */
 int gpf_lml_hyper_batch(gpf_ctx* ctx, const double* th_Pd2, int P, double* lml_P, double* grad_Pd2,
                         double* q_P, int* status_P, int* bad_idx);
+
+/* A marginalised polynomial mean function (Rasmussen & Williams 2.7): f(x) = h(x)^T beta + g(x) with g
+ * the GP of every other call, h(x) the m basis functions the caller evaluates, and beta integrated
+ * out under a flat prior.
+ *
+ * gpf_set_basis: H_mN is (m, N) row-major, the basis at the training points, kept on the device like
+ * the data. GPF_BAD_ARG for a null ctx or H_mN, no data set, m < 1, m > 32, m >= N or an entry that
+ * is not finite; the basis set before then stays in force. Every gpf_set_data discards the basis (it
+ * belongs to the points it was evaluated at): gpf_lml_mean_batch and gpf_predict_mean then return
+ * GPF_BAD_ARG until it is set again. H must have full row rank (the Python binding checks it; here a
+ * rank-deficient H shows as GPF_NOT_PD in the calls below). */
+int gpf_set_basis(gpf_ctx* ctx, const double* H_mN, int m);
+
+/* The restricted log marginal likelihood (REML: beta integrated out) and its gradient in (l, a, s), for
+ * a batch of particles. th_Pd2 as gpf_lml_hyper_batch. With Lt = chol(Kt), U = Lt^-1, z = U y,
+ * Z = U H^T, At = Z^T Z = H Kt^-1 H^T = La La^T, Zo = Z La^-T, t = Zo^T z, zr = z - Zo t, Q' = zr^T zr,
+ * Bt = Zo^T U, Pt = U^T U - Bt^T Bt, at = Pt y, pt_i = Pt_ii and S' = sum_i e_i^2 (at_i^2 / a^2 - pt_i):
+ *   lml_P[p]         = -Q' / (2 a^2) - sum log Lt_ii - sum log La_rr - (N - m) log a - (N - m)/2 log(2 pi)
+ *   grad_Pd2[p,k<d]  = sum_{i>j} (at_i at_j / a^2 - Pt_ij) K_ij (x_ik - x_jk)^2 / l_k^3
+ *   grad_Pd2[p,d]    = dLML/da = (Q' / a^2 - (N - m)) / a - (s^2 / a^3) S'
+ *   grad_Pd2[p,d+1]  = dLML/ds = (s / a^2) S'                       (grad_Pd2 nullable: no O(N^3) pass)
+ *   beta_Pm[p]       = La^-T t, the generalised-least-squares coefficients; they do not depend on a (nullable)
+ *   q_P[p]           = Q': for fixed (l, r) the best amplitude is a^2 = Q' / (N - m) (nullable)
+ *   status_P[p]      = GPF_OK or GPF_NOT_PD (nullable)
+ * Q' is formed as the residual's sum of squares, so a large offset in y costs no digits of it.
+ * A particle whose Kt, or whose At, has a pivot <= 0 is GPF_NOT_PD as in gpf_lml_hyper_batch (-inf,
+ * NaN rows; the others are computed; *bad_idx the first); gpf_last_error says which of the two failed.
+ * Argument checks, P == 0 and the same bits on a repeated call are gpf_lml_hyper_batch's, and
+ * GPF_BAD_ARG also when no basis is set. lml, q and beta do not depend on whether the gradient is
+ * asked for. The call keeps its own buffers: it changes no bit of any other call. */
+int gpf_lml_mean_batch(gpf_ctx* ctx, const double* th_Pd2, int P, double* lml_P, double* grad_Pd2,
+                       double* beta_Pm, double* q_P, int* status_P, int* bad_idx);
+
+/* gpf_predict with the mean function, for the unit model a = s = 1 ((a, s) go through the data as in
+ * gpfit.amplitude.scaled_data; beta scales by a). hfit_mM is (m, M) row-major, the basis at the query
+ * points. With k_q = K_s[:, q], h_q the basis at query point q and R_q = h_q - H Kt^-1 k_q:
+ *   mu_M[q] = k_q^T at + h_q^T beta
+ *   sd_M[q] = sqrt(max(1 - sum v^2, 1e-12) + |La^-1 R_q|^2)
+ * the first term gpf_predict's variance and clip, the second the share of not knowing beta.
+ * beta_m (nullable): beta; bcov_mm (nullable, (m, m) row-major): cov(beta) = At^-1.
+ * The query axis is chunked as gpf_predict's (batch), and the chunking does not change the bits.
+ * M == 0 returns GPF_OK and writes nothing; on GPF_NOT_PD (Kt or At) no output is touched. The buffers
+ * are a kept set of the call's own under GPF_PREDICT_KEEP_MB.
+ * Not built: the mean function in gpf_predict_cov, the draws, gpf_predict_linear,
+ * gpf_predict_conditioned, gpf_predict_batch, the length-scale sampler and leave-one-out; the m dot
+ * products Z^T V folded into k_predict_vsq's register reduction (it would save the K_s^T Bt^T pass;
+ * that kernel sits at 124 of 128 VGPRs); bases other than what the caller puts into H. */
+int gpf_predict_mean(gpf_ctx* ctx, const double* ls_d, const double* xfit_dM, const double* hfit_mM, int64_t M,
+                     int64_t batch, double* mu_M, double* sd_M, double* beta_m, double* bcov_mm);
 
 /* gpf_predict for P length-scale samples at once, and their mixture: the length scales are not known
  * exactly (the fit ends with many nearly-as-good candidates), so the prediction is taken at P samples
