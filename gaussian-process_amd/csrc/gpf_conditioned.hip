@@ -14,6 +14,7 @@
 #pragma once
 #include "gpf_common.hip"
 #include "gpf_linear.hip"
+#include "gpf_predict.hip"
 
 namespace gpf {
 
@@ -66,7 +67,7 @@ __global__ __launch_bounds__(NTHR) void k_con_g(int Rp, const double* __restrict
 }
 
 // The conditioned mean and standard deviation of the query points of one chunk, one thread per
-// point: mu and 1 - sum v^2 from the row-tile partials in order (as k_predict_out), then
+// point: mu and 1 - sum v^2 from the row-tile partials (row_tile_sums, as k_predict_out), then
 //   mu' = mu + sum_r E[q][r] g_r,   var' = (1 - sum v^2) - sum_r E[q][r]^2,   r ascending,
 // clipped at 1e-12 (GP_func.py:39-40). R4: R rounded up to 4 (E's and g's padding is exact zeros).
 // chi2 (nullptr on all chunks but the first): g . g, written by the first thread.
@@ -77,10 +78,8 @@ __global__ __launch_bounds__(NTHR) void k_con_out(int nt, int m, const double* _
                                                   double* __restrict__ sd, double* __restrict__ chi2) {
   const int q = blockIdx.x * NTHR + threadIdx.x;
   if (q >= m) return;
-  double mq = 0.0;
-  for (int t = 0; t < nt; ++t) mq = mq + vz[(size_t)t * ldks + q];
-  double s = 0.0;
-  for (int t = 0; t < nt; ++t) s = s + vsq[(size_t)t * ldks + q];
+  double mq, s;
+  row_tile_sums(nt, vz, vsq, ldks, q, mq, s);
   const d4* e4 = reinterpret_cast<const d4*>(E + (size_t)q * lde);
   double eg = 0.0, e2 = 0.0;
   for (int r = 0; r < R4; r += 4) {

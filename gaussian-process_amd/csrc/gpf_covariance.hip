@@ -121,12 +121,12 @@ __global__ __launch_bounds__(NTHR) void k_build_cov(int N, int Npad, int d, cons
 // 4.7 -> 4.9 TB/s)
 constexpr int CC_R = 32, CC_C = 256;
 __host__ __device__ constexpr size_t cross_cov_lds(int d) { return (size_t)(d + 1) * (CC_R + CC_C) * 8; }
+// The block (blockIdx.y, blockIdx.x) of the output: the body of k_cross_cov and, with a particle's
+// l and out, of k_cross_cov_batch (gpf_predbatch.hip).
 template <int D>
-__global__ __launch_bounds__(NTHR) void k_cross_cov(int N1, int N2, int R, int C, int dd,
-                                                    const double* __restrict__ x1, int ld1,
-                                                    const double* __restrict__ x2, int ld2,
-                                                    const double* __restrict__ l, double* __restrict__ out,
-                                                    int64_t ldo) {
+__device__ __forceinline__ void cross_cov_block(int N1, int N2, int R, int C, int dd, const double* __restrict__ x1,
+                                                int ld1, const double* __restrict__ x2, int ld2,
+                                                const double* __restrict__ l, double* __restrict__ out, int64_t ldo) {
   const int d = D > 0 ? D : dd;
   extern __shared__ double cc_lds[];
   double* ai = cc_lds;                  // [d][CC_R]
@@ -184,6 +184,28 @@ __global__ __launch_bounds__(NTHR) void k_cross_cov(int N1, int N2, int R, int C
   }
 }
 
+template <int D>
+__global__ __launch_bounds__(NTHR) void k_cross_cov(int N1, int N2, int R, int C, int dd,
+                                                    const double* __restrict__ x1, int ld1,
+                                                    const double* __restrict__ x2, int ld2,
+                                                    const double* __restrict__ l, double* __restrict__ out,
+                                                    int64_t ldo) {
+  cross_cov_block<D>(N1, N2, R, C, dd, x1, ld1, x2, ld2, l, out, ldo);
+}
+
+// The run-time dimension d as the kernels' template constant: f(std::integral_constant<int, D>) with
+// D = d for d in 1..4 and D = 0 (any d <= DMAX at run time) otherwise
+template <typename F>
+inline void with_cross_cov_dim(int d, F f) {
+  switch (d) {
+    case 1: f(std::integral_constant<int, 1>()); break;
+    case 2: f(std::integral_constant<int, 2>()); break;
+    case 3: f(std::integral_constant<int, 3>()); break;
+    case 4: f(std::integral_constant<int, 4>()); break;
+    default: f(std::integral_constant<int, 0>()); break;
+  }
+}
+
 // k_cross_cov for dimension d on `stream` (grid and LDS as above). (r4: a form with two columns per
 // lane, 16-B non-temporal stores and row blocks strided over a resident grid was bitwise equal and
 // 3-5% slower on the prediction's 331 MB K_s — the kernel is bound by its exp() issue, not by the
@@ -193,14 +215,10 @@ __global__ __launch_bounds__(NTHR) void k_cross_cov(int N1, int N2, int R, int C
 inline void launch_cross_cov(hipStream_t stream, int N1, int N2, int R, int C, int d, const double* x1, int ld1,
                              const double* x2, int ld2, const double* l, double* out, int64_t ldo) {
   const dim3 grid((unsigned)((C + CC_C - 1) / CC_C), (unsigned)((R + CC_R - 1) / CC_R));
-  const size_t lds = cross_cov_lds(d);
-  switch (d) {
-    case 1: hipLaunchKernelGGL(k_cross_cov<1>, grid, dim3(NTHR), lds, stream, N1, N2, R, C, d, x1, ld1, x2, ld2, l, out, ldo); break;
-    case 2: hipLaunchKernelGGL(k_cross_cov<2>, grid, dim3(NTHR), lds, stream, N1, N2, R, C, d, x1, ld1, x2, ld2, l, out, ldo); break;
-    case 3: hipLaunchKernelGGL(k_cross_cov<3>, grid, dim3(NTHR), lds, stream, N1, N2, R, C, d, x1, ld1, x2, ld2, l, out, ldo); break;
-    case 4: hipLaunchKernelGGL(k_cross_cov<4>, grid, dim3(NTHR), lds, stream, N1, N2, R, C, d, x1, ld1, x2, ld2, l, out, ldo); break;
-    default: hipLaunchKernelGGL(k_cross_cov<0>, grid, dim3(NTHR), lds, stream, N1, N2, R, C, d, x1, ld1, x2, ld2, l, out, ldo); break;
-  }
+  with_cross_cov_dim(d, [&](auto D) {
+    hipLaunchKernelGGL(k_cross_cov<D()>, grid, dim3(NTHR), cross_cov_lds(d), stream, N1, N2, R, C, d, x1, ld1, x2, ld2, l, out,
+                       ldo);
+  });
 }
 
 }  // namespace gpf

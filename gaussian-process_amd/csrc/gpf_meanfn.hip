@@ -24,6 +24,7 @@
 #pragma once
 #include "gpf_common.hip"
 #include "gpf_lmlgrad.hip"
+#include "gpf_predict.hip"
 
 namespace gpf {
 
@@ -465,8 +466,8 @@ __global__ __launch_bounds__(Geo<T>::NTH, 4) void k_mean_grad(int N, int Npad, i
 }
 
 // gpf_predict_mean's outputs for the query points of one chunk, one thread per point: K_s^T at and
-// 1 - sum v^2 from the row-tile partials in k_predict_out's order (k_predict_vsq ran with zr in z's
-// place) and its clip, then with w = Lai h_q (row r: k ascending)
+// 1 - sum v^2 from the row-tile partials (row_tile_sums; k_predict_vsq ran with zr in z's place)
+// with k_predict_out's clip, then with w = Lai h_q (row r: k ascending)
 //   mu_q = K_s[:, q]^T at + h_q^T beta,   var_q = max(1 - sum v^2, 1e-12) + sum_r (w_r - (Bt K_s[:, q])_r)^2,
 // r ascending: the second term is |La^-1 R_q|^2 with R_q = h_q - G^T K_s[:, q], G^T = La Bt.
 // hq: [m][ldks] the basis at the chunk's points. kb: [chunk][ldb] = K_s^T Bt^T. Lai: k_mean_small's La^-1.
@@ -482,10 +483,8 @@ __global__ __launch_bounds__(NTHR) void k_mean_out(int nt, int M, int m, const d
   __syncthreads();
   const int q = blockIdx.x * NTHR + threadIdx.x;
   if (q >= M) return;
-  double mq = 0.0;
-  for (int t = 0; t < nt; ++t) mq = mq + vz[(size_t)t * ldks + q];
-  double s = 0.0;
-  for (int t = 0; t < nt; ++t) s = s + vsq[(size_t)t * ldks + q];
+  double mq, s;
+  row_tile_sums(nt, vz, vsq, ldks, q, mq, s);
   double var = 1.0 - s;
   var = (var < 1e-12) ? 1e-12 : var;
   double hb = 0.0, e2 = 0.0;

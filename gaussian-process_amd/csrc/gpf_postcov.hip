@@ -6,48 +6,21 @@
 // FP64 MFMA, k_mirror_lower copies the lower triangle over the upper one.
 #pragma once
 #include "gpf_common.hip"
+#include "gpf_predict.hip"
 
 namespace gpf {
 
 // k_predict_vsq (gpf_predict.hip) plus a store of every tile of V: V row-major Npad x ldks (the
-// leading dimension of K_s). The same GEMM and the same reductions in the same order, so vsq / vz
-// — and the mean k_predict_out sums from vz — are bitwise gpf_predict's. A kernel of its own:
-// k_predict_vsq compiles as before. The padded rows of U are identity rows over zero rows of K_s
-// and the padded query columns of K_s are zero, so V's padding holds exact zeros.
+// leading dimension of K_s). Both kernels are predict_tile, so vsq / vz — and the mean
+// k_predict_out sums from vz — are bitwise gpf_predict's. The padded rows of U are identity rows
+// over zero rows of K_s and the padded query columns of K_s are zero, so V's padding holds exact zeros.
 // grid: (nqt, nt)
 __global__ __launch_bounds__(Geo<T>::NTH, 4) void k_predict_v(int Npad, const double* __restrict__ U,
                                                        const double* __restrict__ Ks, int ldks,
                                                        double* __restrict__ vsq, const double* __restrict__ z,
                                                        double* __restrict__ vz, double* __restrict__ V) {
-  __shared__ __attribute__((aligned(16))) double smem[DL_STAGE];
-  const int q = blockIdx.x, t = (int)gridDim.y - 1 - (int)blockIdx.y;  // the deepest row tiles first
-  const Quad<T> qd;
-  Acc<T> acc;
-  acc.zero();
-  gemm_stream_dl<true, false, TRI_A_LAST, 2, false>(acc, U + (size_t)t * T * Npad, Npad, Ks + (size_t)q * T, ldks, (t + 1) * T,
-                                                    smem, qd);
-  acc.store(qd, V + (size_t)t * T * ldks + (size_t)q * T, (size_t)ldks);
-  constexpr int MBR = Geo<T>::MBR;
-  const double* zt = z + (size_t)t * T + (qd.lane >> 4);
-  double half[2], zh[2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    double a2 = 0.0, az = 0.0;
-#pragma unroll
-    for (int mi = h * MBR / 2; mi < (h + 1) * MBR / 2; ++mi)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        a2 = fma(acc.v[mi][0][r], acc.v[mi][0][r], a2);
-        az = fma(acc.v[mi][0][r], zt[mi * 16 + 4 * r], az);
-      }
-    half[h] = sum_lane_groups(a2);
-    zh[h] = sum_lane_groups(az);
-  }
-  if ((qd.lane >> 4) == 0) {
-    const size_t o = (size_t)t * ldks + (size_t)q * T + qd.col(0);
-    vsq[o] = half[0] + half[1];
-    vz[o] = zh[0] + zh[1];
-  }
+  // the deepest row tiles first
+  predict_tile<true, false>(Npad, U, Ks, ldks, vsq, z, vz, V, blockIdx.x, (int)gridDim.y - 1 - (int)blockIdx.y);
 }
 
 // Lower tile (I, J <= I) of Sigma = K_ss - V^T V: acc = V[:, I]^T V[:, J] over depth Npad, both

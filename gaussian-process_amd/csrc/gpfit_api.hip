@@ -665,6 +665,101 @@ static int64_t largest_tiled(int64_t hi, F ok) {
   return fit;
 }
 
+// "... need X MiB<at>, more than half of the free Y MiB of device memory; <largest> <fit>": the end of
+// every budget message of the two acquisition helpers below
+static int over_budget(gpf_ctx* c, const std::string& what, double total, const char* at, const Budget& bg,
+                       const char* largest, int64_t fit) {
+  c->err = what + " need " + std::to_string((long long)(total / 1048576.0)) + " MiB" + at + ", more than half of the free " +
+           std::to_string((long long)(bg.fr / 1048576)) + " MiB of device memory; " + largest + std::to_string(fit);
+  return GPF_BAD_ARG;
+}
+
+// The kept set of a call that does not chunk over M (gpf_predict_cov, gpf_posterior_draws): the set
+// plan(Cp) lays out must fit half of the free memory whole, the set's own given back first.
+// what: the message's "<entry point>: <buffers> for M=.. at N=..".
+template <typename F>
+static int acquire_whole(gpf_ctx* c, KeptSet& ks, int64_t Cp, int nbuf, unsigned pinned, F plan, const std::string& what) {
+  const SetPlan p = plan(Cp);
+  if (ks.fits(p.bytes, nbuf)) return GPF_OK;
+  Budget bg;
+  if (int rb = half_free(c, &ks, &bg)) return rb;
+  if (p.total > bg.half)
+    return over_budget(c, what, p.total, "", bg, "the largest M that fits is ",
+                       largest_tiled(Cp, [&](int64_t cols) { return plan(cols).total <= bg.half; }));
+  return ks.regrow(c, p.bytes, pinned, nbuf);
+}
+
+// The kept set of a call that folds the query axis away `chunk` points per pass (gpf_predict_linear,
+// gpf_predict_conditioned): the caller's chunk, or gpf_predict's default, in whole tiles (the block's
+// leading dimension and the byte offsets of the streamed panels stay well inside 32 bits); where
+// the set plan(M, Cc) lays out does not fit half of the free memory (the set's own given back first)
+// the chunk is halved down to one tile, and then the call fails. *out: the plan the set now fits.
+template <typename F, typename P>
+static int acquire_chunked(gpf_ctx* c, KeptSet& ks, int nbuf, const char* fn, int64_t M, int R, int64_t chunk, F plan,
+                           P* out) {
+  const int64_t Mp = ((M + T - 1) / T) * T;
+  int64_t Cc = std::min<int64_t>(chunk > 0 ? chunk : 16384, 65536);
+  Cc = std::min(((Cc + T - 1) / T) * T, Mp);
+  P p = plan(M, Cc);
+  if (!ks.fits(p.bytes, nbuf)) {
+    Budget bg;
+    if (int rb = half_free(c, &ks, &bg)) return rb;
+    while (p.total > bg.half && Cc > T) {  // fewer query points per pass
+      Cc = std::max<int64_t>(T, ((Cc / 2 + T - 1) / T) * T);
+      p = plan(M, Cc);
+    }
+    if (p.total > bg.half)
+      return over_budget(c, std::string(fn) + ": the weights, the coordinates and the operands for M=" + std::to_string(M) +
+                                ", R=" + std::to_string(R) + " at N=" + std::to_string(c->N),
+                         p.total, " at 128 query points per pass", bg, "the largest M that fits at this R is ",
+                         largest_tiled(Mp, [&](int64_t m) { return plan(m, T).total <= bg.half; }));
+    if (int rg = ks.regrow(c, p.bytes, 0, nbuf)) return rg;
+  }
+  *out = p;
+  return GPF_OK;
+}
+
+// What every posterior entry point does between its argument checks and its own work: the device, a
+// minimal histogram (the objective grid is not needed), the knobs and, with slots > 0, a factorisation
+// workspace of that many particles (first: a (re)allocation there frees the kept sets too)
+static int posterior_open(gpf_ctx* c, int slots, Knobs* knobs) {
+  hipSetDevice(c->device);
+  if (c->K <= 0) c->K = 2;
+  *knobs = Knobs::from_env();
+  return slots > 0 ? ensure_work(c, slots, *knobs) : GPF_OK;
+}
+
+// ... and at its end: the stream drained, the profile folded in, and the set kept for the next call
+// only while it is modest (a huge batch_size can size it up to half of free HBM; see keep_bytes)
+static int posterior_close(gpf_ctx* c, KeptSet& ks, const Knobs& knobs, int rc) {
+  hipStreamSynchronize(c->stream);
+  if (c->prof) harvest(c);
+  ks.trim(knobs);
+  return rc;
+}
+
+// The flops of V = U K_s over every row tile of U at `cols` padded columns (row tile t has t+1
+// column tiles, the last triangular)
+static double v_flops(int nt, int64_t cols) {
+  return 2.0 * T * T * (double)cols * ((double)nt * (nt + 1) / 2) - (double)T * T * cols * nt;
+}
+
+// K_s of the m query points xq (coordinates with the leading dimension ldx) into ks (Np x ceil(m / 128)
+// tiles, leading dimension ldks), then the row-tile partials of V = U K_s and V^T z (k_predict_vsq)
+static int queue_ks_vsq(gpf_ctx* c, int64_t m, const double* xq, int64_t ldx, double* ks, int64_t ldks, const double* z,
+                        double* vsq, double* vz) {
+  const int64_t Np = c->Npad;
+  const int nqt = (int)((m + T - 1) / T), Cm = nqt * T;
+  int rc = launch(c, PC_PREDK, 8.0 * Np * Cm, [&] {
+    gpf::launch_cross_cov(c->stream, (int)c->N, (int)m, (int)Np, Cm, c->d, c->d_x, (int)c->N, xq, (int)ldx, c->d_ls, ks, ldks);
+  });
+  if (rc) return rc;
+  return launch(c, PC_PRED, v_flops(c->nt, Cm), [&] {
+    hipLaunchKernelGGL(gpf::k_predict_vsq, dim3(nqt, c->nt), dim3(gpf::Geo<T>::NTH), 0, c->stream, (int)Np, c->d_U, ks, (int)ldks,
+                       vsq, z, vz, 0);
+  });
+}
+
 extern "C" {
 
 #ifndef GPF_BUILD_INFO
@@ -990,110 +1085,129 @@ static SetPlan pred_plan(const gpf_ctx* c, int64_t Cp) {
   return p;
 }
 
+// One prediction call that walks the query points in chunks (gpf_predict, gpf_predict_mean): what
+// predict_chunks needs from its entry point. The set's first PRED_NBUF buffers are gpf_predict's
+// (`plan` starts from pred_plan). The hooks run once the set is acquired, and queue on c->stream.
+struct Prediction {
+  const char* fn;  // the entry point, for the messages
+  KeptId set;
+  SetPlan (*plan)(const gpf_ctx*, int64_t Cp);
+  int nbuf;
+  unsigned pinned;
+  int64_t col_bytes;  // device bytes per query column that grow with the chunk (the chunk that fits half of free memory)
+  const double *ls, *xfit;
+  int64_t M, batch;
+  double *mu, *sd;
+  // optional: nrows more rows of M values per query point, staged beside the coordinates through the
+  // pinned buffer rows_host into the device buffer rows_dev (leading dimension Cp)
+  const double* rows = nullptr;
+  int nrows = 0, rows_host = 0, rows_dev = 0;
+  std::function<int()> before_factor, after_factor;  // optional: the call's own uploads and kernels around the factorisation
+  std::function<const double*()> z;                  // optional: k_predict_vsq's z (default: z = U y of slot 0)
+  // the chunk's launches behind k_predict_vsq: (mu, sd) of the m points from query point s on into PRED_MU / PRED_SD
+  std::function<int(int64_t s, int64_t m, int64_t Cp)> out;
+  // optional: a failure of the call's own, from what `out` copied back at s = 0 (it sets c->err); asked
+  // after the factorisation's status
+  std::function<int()> first_check;
+};
+
+// The chunks of a prediction: the chunk sized and the set acquired, the length scales and chunk 0's
+// coordinates queued ahead of the factorisation, then per chunk K_s, k_predict_vsq, the call's
+// kernels and the copy back. Nothing reaches q.mu / q.sd before the factorisation's status and the
+// call's own check have passed on chunk 0.
+static int predict_chunks(gpf_ctx* c, const Prediction& q) {
+  Knobs knobs;
+  if (int ro = posterior_open(c, 1, &knobs)) return ro;
+  KeptSet& ks = c->kept[q.set];
+  const int64_t M = q.M;
+  // Query chunk: as large as memory allows (the reference's batch_size only bounds its
+  // own host memory, GP_func.py:28-30; results do not depend on it). Sized before the
+  // factorisation is queued, so that a (re)allocation never waits for it; free memory is only
+  // queried when the kept buffers are too small.
+  int64_t chunk = std::min<int64_t>(std::max<int64_t>(std::max<int64_t>(q.batch, 1), 16384), M);
+  int64_t Cp = ((chunk + T - 1) / T) * T;
+  // buffers kept from the previous call when they are large enough (a hipMalloc/hipFree of the
+  // Np x Cp cross-covariance per call cost ~1 ms of the call's wall time); pinned host staging
+  // for the query coordinates and the outputs (pageable copies stage through a bounce buffer)
+  SetPlan p = q.plan(c, Cp);
+  if (!ks.fits(p.bytes, q.nbuf)) {
+    Budget bg;
+    if (int rb = half_free(c, nullptr, &bg)) return rb;
+    const int64_t maxcols = std::max<int64_t>(T, (int64_t)(bg.half / (double)q.col_bytes));
+    chunk = std::min<int64_t>(chunk, maxcols);
+    Cp = ((chunk + T - 1) / T) * T;
+    p = q.plan(c, Cp);
+    if (!ks.fits(p.bytes, q.nbuf))
+      if (int rg = ks.regrow(c, p.bytes, q.pinned, q.nbuf)) return rg;
+  }
+  // (Two overlaps of V = U K_s with the single-particle factorisation were built and measured in
+  // round 4 — V's row tiles on a low-priority side stream behind each factor launch, and the same
+  // with the CUs partitioned by stream CU masks — and removed: the factorisation's latency-bound
+  // chain needs the whole chip, profiles/r4/ab_r4g_summary.txt, ab_pred_cumask.txt.)
+  double *d_xf = ks.as(PRED_XF), *d_mu = ks.as(PRED_MU), *d_sd = ks.as(PRED_SD), *hx = ks.as(PRED_HX), *hout = ks.as(PRED_HOUT);
+  auto stage_chunk = [&](int64_t s0, int64_t m) -> int {
+    for (int k = 0; k < c->d; ++k) std::memcpy(hx + (size_t)k * Cp, q.xfit + (size_t)k * M + s0, (size_t)m * 8);
+    for (int r = 0; r < q.nrows; ++r) std::memcpy(ks.as(q.rows_host) + (size_t)r * Cp, q.rows + (size_t)r * M + s0, (size_t)m * 8);
+    GPF_HIP(c, hipMemcpyAsync(d_xf, hx, (size_t)c->d * Cp * 8, hipMemcpyHostToDevice, c->stream));
+    if (q.nrows)
+      GPF_HIP(c, hipMemcpyAsync(ks.as(q.rows_dev), ks.as(q.rows_host), (size_t)q.nrows * Cp * 8, hipMemcpyHostToDevice, c->stream));
+    return GPF_OK;
+  };
+  // the length scales and chunk 0's coordinates first, then the factorisation
+  std::memcpy(c->h_ls, q.ls, (size_t)c->d * 8);
+  GPF_HIP(c, hipMemcpyAsync(c->d_ls, c->h_ls, (size_t)c->d * 8, hipMemcpyHostToDevice, c->stream));
+  int rc = stage_chunk(0, std::min<int64_t>(chunk, M));
+  if (!rc && q.before_factor) rc = q.before_factor();
+  if (!rc) rc = factor_single_async(c, nullptr, nullptr, knobs);
+  if (!rc && q.after_factor) rc = q.after_factor();
+  if (rc) return rc;
+  const double* d_z = q.z ? q.z() : c->d_yb;
+  for (int64_t s = 0; s < M && rc == GPF_OK; s += chunk) {
+    const int64_t m = std::min<int64_t>(chunk, M - s);
+    if (s > 0) {
+      if (hipStreamSynchronize(c->stream) != hipSuccess) {  // the staging buffers are reused
+        rc = GPF_HIP_ERROR;
+        break;
+      }
+      if ((rc = stage_chunk(s, m))) break;
+    }
+    if ((rc = queue_ks_vsq(c, m, d_xf, Cp, ks.as(PRED_KS), Cp, d_z, ks.as(PRED_VSQ), ks.as(PRED_VZ)))) break;
+    if ((rc = q.out(s, m, Cp))) break;
+    if (hipMemcpyAsync(hout, d_mu, (size_t)m * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipMemcpyAsync(hout + Cp, d_sd, (size_t)m * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess) {
+      rc = GPF_HIP_ERROR;
+      c->err = std::string(q.fn) + ": copy back failed";
+      break;
+    }
+    if (s == 0) {  // the factorisation's status (its copy preceded this synchronisation), then the call's own
+      rc = particle_status(c, 0);
+      if (!rc && q.first_check) rc = q.first_check();
+      if (rc) break;
+    }
+    std::memcpy(q.mu + s, hout, (size_t)m * 8);
+    std::memcpy(q.sd + s, hout + Cp, (size_t)m * 8);
+  }
+  return posterior_close(c, ks, knobs, rc);
+}
+
 int gpf_predict(gpf_ctx* c, const double* ls, const double* xfit, int64_t M, int64_t batch, double* mu,
                 double* sd) {
   if (!c) return GPF_BAD_ARG;
   if (c->N <= 0) return bad_arg(c, "gpf_predict: call gpf_set_data first");
   if (M < 0 || (M > 0 && (!xfit || !mu || !sd)) || !ls) return bad_arg(c, "gpf_predict: bad arguments");
   if (M == 0) return GPF_OK;
-  hipSetDevice(c->device);
-  if (c->K <= 0) {  // predict does not need the objective grid; size the histogram minimally
-    c->K = 2;
-  }
-  // Query chunk: as large as memory allows (the reference's batch_size only bounds its
-  // own host memory, GP_func.py:28-30; results do not depend on it). Sized before the
-  // factorisation is queued, so that a (re)allocation never waits for it; free memory is only
-  // queried when the kept buffers are too small.
-  // the factorisation workspace first: a (re)allocation there frees the kept sets too
-  const Knobs knobs = Knobs::from_env();
-  if (int rw = ensure_work(c, 1, knobs)) return rw;
   KeptSet& ks = c->kept[KEPT_PRED];
-  const int64_t Np = c->Npad;
-  int64_t chunk = std::min<int64_t>(std::max<int64_t>(std::max<int64_t>(batch, 1), 16384), M);
-  int64_t Cp = ((chunk + T - 1) / T) * T;
-  // buffers kept from the previous call when they are large enough (a hipMalloc/hipFree of the
-  // Np x Cp cross-covariance per call cost ~1 ms of the call's wall time); pinned host staging
-  // for the query coordinates and the outputs (pageable copies stage through a bounce buffer)
-  SetPlan p = pred_plan(c, Cp);
-  if (!ks.fits(p.bytes, PRED_NBUF)) {
-    Budget bg;
-    if (int rb = half_free(c, nullptr, &bg)) return rb;
-    const int64_t per_col = (Np + 2 * c->nt) * 8;
-    const int64_t maxcols = std::max<int64_t>(T, (int64_t)(bg.half / (double)per_col));
-    chunk = std::min<int64_t>(chunk, maxcols);
-    Cp = ((chunk + T - 1) / T) * T;
-    p = pred_plan(c, Cp);
-    if (!ks.fits(p.bytes, PRED_NBUF))
-      if (int rg = ks.regrow(c, p.bytes, PRED_PINNED, PRED_NBUF)) return rg;
-  }
-  // (Two overlaps of V = U K_s with the single-particle factorisation were built and measured in
-  // round 4 — V's row tiles on a low-priority side stream behind each factor launch, and the same
-  // with the CUs partitioned by stream CU masks — and removed: the factorisation's latency-bound
-  // chain needs the whole chip, profiles/r4/ab_r4g_summary.txt, ab_pred_cumask.txt.)
-  double *d_xf = ks.as(PRED_XF), *d_ks = ks.as(PRED_KS), *d_vsq = ks.as(PRED_VSQ), *d_vz = ks.as(PRED_VZ);
-  double *d_mu = ks.as(PRED_MU), *d_sd = ks.as(PRED_SD), *hx = ks.as(PRED_HX), *hout = ks.as(PRED_HOUT);
-  const double* d_z = c->d_yb;  // z = U y of particle slot 0
-  auto stage_chunk = [&](int64_t s0, int64_t m) -> int {
-    for (int k = 0; k < c->d; ++k) std::memcpy(hx + (size_t)k * Cp, xfit + (size_t)k * M + s0, (size_t)m * 8);
-    GPF_HIP(c, hipMemcpyAsync(d_xf, hx, (size_t)c->d * Cp * 8, hipMemcpyHostToDevice, c->stream));
-    return GPF_OK;
+  Prediction q{"gpf_predict", KEPT_PRED, pred_plan, PRED_NBUF, PRED_PINNED, (c->Npad + 2 * c->nt) * 8, ls, xfit, M, batch, mu, sd};
+  q.out = [&](int64_t, int64_t m, int64_t Cp) {
+    return launch(c, PC_LOSS, 0.0, [&] {
+      hipLaunchKernelGGL(gpf::k_predict_out, dim3((unsigned)((m + NTHR - 1) / NTHR)), dim3(NTHR), 0, c->stream, c->nt, (int)m,
+                         ks.as(PRED_VZ), (int)Cp, ks.as(PRED_VSQ), ks.as(PRED_MU), ks.as(PRED_SD));
+    });
   };
-  // the length scales and chunk 0's coordinates first, then the factorisation
-  std::memcpy(c->h_ls, ls, (size_t)c->d * 8);
-  GPF_HIP(c, hipMemcpyAsync(c->d_ls, c->h_ls, (size_t)c->d * 8, hipMemcpyHostToDevice, c->stream));
-  int rc = stage_chunk(0, std::min<int64_t>(chunk, M));
-  if (rc) return rc;
-  rc = factor_single_async(c, nullptr, nullptr, knobs);
-  if (rc) return rc;
-  for (int64_t s = 0; s < M && rc == GPF_OK; s += chunk) {
-    const int64_t m = std::min<int64_t>(chunk, M - s);
-    const int nqt = (int)((m + T - 1) / T);
-    const int Cm = nqt * T;
-    if (s > 0) {
-      if (hipStreamSynchronize(c->stream) != hipSuccess) {  // the staging buffer is reused
-        rc = GPF_HIP_ERROR;
-        break;
-      }
-      if ((rc = stage_chunk(s, m))) break;
-    }
-    rc = launch(c, PC_PREDK, 8.0 * Np * Cm, [&] {
-      gpf::launch_cross_cov(c->stream, (int)c->N, (int)m, (int)Np, Cm, c->d, c->d_x, (int)c->N, d_xf, (int)Cp, c->d_ls,
-                            d_ks, (int64_t)Cp);
-    });
-    if (rc) break;
-    // V = U K_s over every row tile of U (row tile t has t+1 column tiles, the last triangular)
-    const double vflops = 2.0 * T * T * (double)Cm * ((double)c->nt * (c->nt + 1) / 2) - (double)T * T * Cm * c->nt;
-    rc = launch(c, PC_PRED, vflops, [&] {
-      hipLaunchKernelGGL(gpf::k_predict_vsq, dim3(nqt, c->nt), dim3(gpf::Geo<T>::NTH), 0, c->stream, (int)Np, c->d_U,
-                         d_ks, (int)Cp, d_vsq, d_z, d_vz, 0);
-    });
-    if (rc) break;
-    rc = launch(c, PC_LOSS, 0.0, [&] {
-      hipLaunchKernelGGL(gpf::k_predict_out, dim3((unsigned)((m + NTHR - 1) / NTHR)), dim3(NTHR), 0, c->stream, c->nt,
-                         (int)m, d_vz, (int)Cp, d_vsq, d_mu, d_sd);
-    });
-    if (rc) break;
-    if (hipMemcpyAsync(hout, d_mu, (size_t)m * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-        hipMemcpyAsync(hout + Cp, d_sd, (size_t)m * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-        hipStreamSynchronize(c->stream) != hipSuccess) {
-      rc = GPF_HIP_ERROR;
-      c->err = "gpf_predict: copy back failed";
-      break;
-    }
-    if (s == 0) {  // the factorisation's status (its copy preceded this synchronisation)
-      rc = particle_status(c, 0);
-      if (rc) break;
-    }
-    std::memcpy(mu + s, hout, (size_t)m * 8);
-    std::memcpy(sd + s, hout + Cp, (size_t)m * 8);
-  }
-  hipStreamSynchronize(c->stream);
-  if (c->prof) harvest(c);
-  // keep the query-chunk buffers for the next call only while they are modest (a huge batch_size
-  // can size them up to half of free HBM; see keep_bytes)
-  ks.trim(knobs);
-  return rc;
+  return predict_chunks(c, q);
 }
+
 
 // gpf_predict_cov's kept buffers, and gpf_posterior_draws': a set like it with its own behind
 enum PcovBuf {
@@ -1157,10 +1271,9 @@ static int pcov_enqueue(gpf_ctx* c, const Knobs& knobs, const double* ls, const 
     gpf::launch_cross_cov(c->stream, (int)M, (int)M, (int)Cp, (int)Cp, c->d, xf, (int)Cp, xf, (int)Cp, c->d_ls,
                           cov, Cp);
   });
-  // V = U K_s, stored (flops as gpf_predict counts them), and its per-column partials
-  const double vflops = 2.0 * T * T * (double)Cp * ((double)c->nt * (c->nt + 1) / 2) - (double)T * T * Cp * c->nt;
+  // V = U K_s, stored, and its per-column partials
   if (!rc)
-    rc = launch(c, PC_PRED, vflops, [&] {
+    rc = launch(c, PC_PRED, v_flops(c->nt, Cp), [&] {
       hipLaunchKernelGGL(gpf::k_predict_v, dim3(nqt, c->nt), dim3(gpf::Geo<T>::NTH), 0, c->stream, (int)Np, c->d_U, ks,
                          (int)Cp, vsq, c->d_yb, vz, v);
     });
@@ -1195,27 +1308,13 @@ int gpf_predict_cov(gpf_ctx* c, const double* ls, const double* xfit, int64_t M,
   if (int rl = check_ls(c, "gpf_predict_cov", ls, (size_t)c->d)) return rl;
   if (M > (int64_t)1 << 24) return bad_arg(c, "gpf_predict_cov: M > 2^24 (Sigma is dense: M x M doubles)");
   if (M == 0) return GPF_OK;
-  hipSetDevice(c->device);
-  if (c->K <= 0) c->K = 2;  // (as gpf_predict: the objective grid is not needed)
-  // the factorisation workspace first: a (re)allocation there frees the query buffers too
-  const Knobs knobs = Knobs::from_env();
-  if (int rw = ensure_work(c, 1, knobs)) return rw;
+  Knobs knobs;
+  if (int ro = posterior_open(c, 1, &knobs)) return ro;
   KeptSet& ks = c->kept[KEPT_PCOV];
   const int64_t Cp = ((M + T - 1) / T) * T;
-  const SetPlan p = pcov_plan(c, Cp);
-  if (!ks.fits(p.bytes, PCOV_NBUF)) {
-    // no chunking over M: K_s, V and Sigma must fit half of free HBM together
-    Budget bg;
-    if (int rb = half_free(c, &ks, &bg)) return rb;
-    if (p.total > bg.half) {
-      const int64_t fit = largest_tiled(Cp, [&](int64_t cols) { return pcov_plan(c, cols).total <= bg.half; });
-      c->err = "gpf_predict_cov: K_s, V and Sigma for M=" + std::to_string(M) + " at N=" + std::to_string(c->N) +
-               " need " + std::to_string((long long)(p.total / 1048576.0)) + " MiB, more than half of the free " +
-               std::to_string((long long)(bg.fr / 1048576)) + " MiB of device memory; the largest M that fits is " + std::to_string(fit);
-      return GPF_BAD_ARG;
-    }
-    if (int rg = ks.regrow(c, p.bytes, PCOV_PINNED, PCOV_NBUF)) return rg;
-  }
+  if (int ra = acquire_whole(c, ks, Cp, PCOV_NBUF, PCOV_PINNED, [&](int64_t cols) { return pcov_plan(c, cols); },
+                             "gpf_predict_cov: K_s, V and Sigma for M=" + std::to_string(M) + " at N=" + std::to_string(c->N)))
+    return ra;
   double *d_mu = ks.as(PCOV_MU), *hmu = ks.as(PCOV_HMU);
   int rc = pcov_enqueue(c, knobs, ls, xfit, M, Cp, ks.p);
   if (!rc && hipMemcpyAsync(hmu, d_mu, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
@@ -1237,9 +1336,7 @@ int gpf_predict_cov(gpf_ctx* c, const double* ls, const double* xfit, int64_t M,
       c->err = "gpf_predict_cov: copy back failed";
     }
   }
-  if (c->prof) harvest(c);
-  ks.trim(knobs);
-  return rc;
+  return posterior_close(c, ks, knobs, rc);
 }
 
 // ---- linear functionals of the posterior (gpf_linear.hip) ----
@@ -1362,9 +1459,8 @@ static int lin_enqueue(gpf_ctx* c, const Knobs& knobs, void* const* bufs, const 
                      });
   }
   // V_A = U B with the mean's partials (sum over the row tiles of V_A^T z = B^T alpha = A mu)
-  const double vflops = 2.0 * T * T * (double)Rp * ((double)nt * (nt + 1) / 2) - (double)T * T * Rp * nt;
   if (!rc)
-    rc = launch(c, PC_PRED, vflops, [&] {
+    rc = launch(c, PC_PRED, v_flops(nt, Rp), [&] {
       hipLaunchKernelGGL(gpf::k_predict_v, dim3(Rt, nt), dim3(gpf::Geo<T>::NTH), 0, st, (int)Np, c->d_U, B, Rp, buf(LIN_VSQ),
                          c->d_yb, buf(LIN_VZ), V);
     });
@@ -1430,34 +1526,13 @@ int gpf_predict_linear(gpf_ctx* c, const double* ls, const double* xfit, int64_t
   if (M == 0 || R == 0) return GPF_OK;
   for (size_t i = 0, n = (size_t)R * (size_t)M; i < n; ++i)
     if (!std::isfinite(w[i])) return bad_arg(c, "gpf_predict_linear: weights must be finite");
-  hipSetDevice(c->device);
-  if (c->K <= 0) c->K = 2;  // (as gpf_predict: the objective grid is not needed)
-  // the factorisation workspace first: a (re)allocation there frees the query buffers too
-  const Knobs knobs = Knobs::from_env();
-  if (int rw = ensure_work(c, 1, knobs)) return rw;
-  // query points per pass: the caller's, or gpf_predict's default, in whole tiles (the block's
-  // leading dimension and the byte offsets of the streamed panels stay well inside 32 bits)
-  int64_t Cc = std::min<int64_t>(chunk > 0 ? chunk : 16384, 65536);
-  Cc = ((Cc + T - 1) / T) * T;
+  Knobs knobs;
+  if (int ro = posterior_open(c, 1, &knobs)) return ro;
   KeptSet& ks = c->kept[KEPT_LIN];
-  LinPlan p = lin_plan(c, M, R, Cc);
-  if (!ks.fits(p.bytes, LIN_NBUF)) {
-    Budget bg;
-    if (int rb = half_free(c, &ks, &bg)) return rb;
-    while (p.total > bg.half && p.Cc > T) {  // fewer query points per pass
-      Cc = std::max<int64_t>(T, ((p.Cc / 2 + T - 1) / T) * T);
-      p = lin_plan(c, M, R, Cc);
-    }
-    if (p.total > bg.half) {
-      const int64_t fit = largest_tiled(p.Mp, [&](int64_t m) { return lin_plan(c, m, R, T).total <= bg.half; });
-      c->err = "gpf_predict_linear: the weights, the coordinates and the operands for M=" + std::to_string(M) + ", R=" +
-               std::to_string(R) + " at N=" + std::to_string(c->N) + " need " + std::to_string((long long)(p.total / 1048576.0)) +
-               " MiB at 128 query points per pass, more than half of the free " + std::to_string((long long)(bg.fr / 1048576)) +
-               " MiB of device memory; the largest M that fits at this R is " + std::to_string(fit);
-      return GPF_BAD_ARG;
-    }
-    if (int rg = ks.regrow(c, p.bytes, 0, LIN_NBUF)) return rg;
-  }
+  LinPlan p;
+  if (int ra = acquire_chunked(c, ks, LIN_NBUF, "gpf_predict_linear", M, R, chunk,
+                               [&](int64_t m, int64_t cc) { return lin_plan(c, m, R, cc); }, &p))
+    return ra;
   const int Rp = p.Rp;
   double *Q = ks.as(LIN_Q), *S = ks.as(LIN_COV), *mu = ks.as(LIN_MU);
   hipStream_t st = c->stream;
@@ -1478,9 +1553,7 @@ int gpf_predict_linear(gpf_ctx* c, const double* ls, const double* xfit, int64_t
       c->err = "gpf_predict_linear: copy back failed";
     }
   }
-  if (c->prof) harvest(c);
-  ks.trim(knobs);
-  return rc;
+  return posterior_close(c, ks, knobs, rc);
 }
 
 // ---- dense Cholesky on the device and posterior draws (gpf_densechol.hip) ----
@@ -1644,29 +1717,15 @@ int gpf_posterior_draws(gpf_ctx* c, const double* ls, const double* xfit, int64_
   if (int rl = check_ls(c, "gpf_posterior_draws", ls, (size_t)c->d)) return rl;
   if (M > (int64_t)1 << 24 || S > (int64_t)1 << 24) return bad_arg(c, "gpf_posterior_draws: M or S > 2^24");
   if (M == 0 || S == 0) return GPF_OK;
-  hipSetDevice(c->device);
-  if (c->K <= 0) c->K = 2;  // (as gpf_predict: the objective grid is not needed)
-  // the factorisation workspace first: a (re)allocation there frees the query buffers too
-  const Knobs knobs = Knobs::from_env();
-  if (int rw = ensure_work(c, 1, knobs)) return rw;
+  Knobs knobs;
+  if (int ro = posterior_open(c, 1, &knobs)) return ro;
   KeptSet& ks = c->kept[KEPT_PDRAW];
   const int nqt = (int)((M + T - 1) / T), nst = (int)((S + T - 1) / T);
   const int64_t Cp = (int64_t)nqt * T, Sp = (int64_t)nst * T;
-  const SetPlan p = pdraw_plan(c, Cp, Sp);
-  if (!ks.fits(p.bytes, PDRAW_NBUF)) {
-    // no chunking over M: everything must fit half of free HBM together
-    Budget bg;
-    if (int rb = half_free(c, &ks, &bg)) return rb;
-    if (p.total > bg.half) {
-      const int64_t fit = largest_tiled(Cp, [&](int64_t cols) { return pdraw_plan(c, cols, Sp).total <= bg.half; });
-      c->err = "gpf_posterior_draws: K_s, V, Sigma, its factor and the draws for M=" + std::to_string(M) + ", S=" +
-               std::to_string(S) + " at N=" + std::to_string(c->N) + " need " +
-               std::to_string((long long)(p.total / 1048576.0)) + " MiB, more than half of the free " +
-               std::to_string((long long)(bg.fr / 1048576)) + " MiB of device memory; the largest M that fits is " + std::to_string(fit);
-      return GPF_BAD_ARG;
-    }
-    if (int rg = ks.regrow(c, p.bytes, PCOV_PINNED, PDRAW_NBUF)) return rg;
-  }
+  if (int ra = acquire_whole(c, ks, Cp, PDRAW_NBUF, PCOV_PINNED, [&](int64_t cols) { return pdraw_plan(c, cols, Sp); },
+                             "gpf_posterior_draws: K_s, V, Sigma, its factor and the draws for M=" + std::to_string(M) +
+                                 ", S=" + std::to_string(S) + " at N=" + std::to_string(c->N)))
+    return ra;
   double *d_mu = ks.as(PCOV_MU), *hmu = ks.as(PCOV_HMU), *d_cov = ks.as(PCOV_COV);
   double *d_L = ks.as(PDRAW_L), *d_z = ks.as(PDRAW_Z), *d_dr = ks.as(PDRAW_DR);
   // (as in gpf_predict_cov, every matrix of the call uses this call's Cp as its leading dimension)
@@ -1717,10 +1776,7 @@ int gpf_posterior_draws(gpf_ctx* c, const double* ls, const double* xfit, int64_
     *jitter_used = jit;
   }
   if (laddered && (rc == GPF_OK || rc == GPF_NOT_PD)) *tries = tr;
-  hipStreamSynchronize(c->stream);
-  if (c->prof) harvest(c);
-  ks.trim(knobs);
-  return rc;
+  return posterior_close(c, ks, knobs, rc);
 }
 
 // ---- the posterior conditioned on measured linear functionals (gpf_conditioned.hip) ----
@@ -1791,35 +1847,15 @@ int gpf_predict_conditioned(gpf_ctx* c, const double* ls, const double* xfit, in
     if (!(sv[r] >= 0.0) || !std::isfinite(sv[r]))
       return bad_arg(c, "gpf_predict_conditioned: the standard errors must be finite and >= 0");
   }
-  hipSetDevice(c->device);
-  if (c->K <= 0) c->K = 2;  // (as gpf_predict: the objective grid is not needed)
-  // the factorisation workspace first: a (re)allocation there frees the query buffers too
-  const Knobs knobs = Knobs::from_env();
-  if (int rw = ensure_work(c, 1, knobs)) return rw;
-  int64_t Cc = std::min<int64_t>(chunk > 0 ? chunk : 16384, 65536);  // (as gpf_predict_linear)
-  Cc = ((Cc + T - 1) / T) * T;
+  Knobs knobs;
+  if (int ro = posterior_open(c, 1, &knobs)) return ro;
   KeptSet& ks = c->kept[KEPT_CON];
-  ConPlan q = con_plan(c, M, R, Cc);
-  if (!ks.fits(q.bytes, CON_NBUF)) {
-    Budget bg;
-    if (int rb = half_free(c, &ks, &bg)) return rb;
-    while (q.total > bg.half && q.lin.Cc > T) {  // fewer query points per pass
-      Cc = std::max<int64_t>(T, ((q.lin.Cc / 2 + T - 1) / T) * T);
-      q = con_plan(c, M, R, Cc);
-    }
-    if (q.total > bg.half) {
-      const int64_t fit = largest_tiled(q.lin.Mp, [&](int64_t m) { return con_plan(c, m, R, T).total <= bg.half; });
-      c->err = "gpf_predict_conditioned: the weights, the coordinates and the operands for M=" + std::to_string(M) + ", R=" +
-               std::to_string(R) + " at N=" + std::to_string(c->N) + " need " + std::to_string((long long)(q.total / 1048576.0)) +
-               " MiB at 128 query points per pass, more than half of the free " + std::to_string((long long)(bg.fr / 1048576)) +
-               " MiB of device memory; the largest M that fits at this R is " + std::to_string(fit);
-      return GPF_BAD_ARG;
-    }
-    if (int rg = ks.regrow(c, q.bytes, 0, CON_NBUF)) return rg;
-  }
+  ConPlan q;
+  if (int ra = acquire_chunked(c, ks, CON_NBUF, "gpf_predict_conditioned", M, R, chunk,
+                               [&](int64_t m, int64_t cc) { return con_plan(c, m, R, cc); }, &q))
+    return ra;
   const LinPlan& p = q.lin;
-  Cc = p.Cc;
-  const int64_t Np = p.Np, Mp = p.Mp;
+  const int64_t Cc = p.Cc, Np = p.Np, Mp = p.Mp;
   const int Rp = p.Rp, Rt = p.Rt, nt = p.nt, d = p.d;
   auto buf = [&](int i) { return ks.as(i); };
   double *G = buf(LIN_G), *xf = buf(LIN_XF), *blk = buf(LIN_BLK), *V = buf(LIN_V), *S = buf(LIN_COV), *amu = buf(LIN_MU);
@@ -1886,16 +1922,7 @@ int gpf_predict_conditioned(gpf_ctx* c, const double* ls, const double* xfit, in
     const int64_t m = std::min<int64_t>(Cc, M - s);
     const int nqt = (int)((m + T - 1) / T);
     const int Cm = nqt * T;
-    rc = launch(c, PC_PREDK, 8.0 * (double)Np * Cm, [&] {
-      gpf::launch_cross_cov(st, (int)c->N, (int)m, (int)Np, Cm, d, c->d_x, (int)c->N, xf + s, (int)Mp, c->d_ls, blk, Cc);
-    });
-    if (rc) break;
-    const double vflops = 2.0 * T * T * (double)Cm * ((double)nt * (nt + 1) / 2) - (double)T * T * Cm * nt;  // (as gpf_predict)
-    rc = launch(c, PC_PRED, vflops, [&] {
-      hipLaunchKernelGGL(gpf::k_predict_vsq, dim3(nqt, nt), dim3(gpf::Geo<T>::NTH), 0, st, (int)Np, c->d_U, blk, (int)Cc, vsq,
-                         c->d_yb, vz, 0);
-    });
-    if (rc) break;
+    if ((rc = queue_ks_vsq(c, m, xf + s, Mp, blk, Cc, c->d_yb, vsq, vz))) break;  // (as gpf_predict)
     // C = G - K_s^T W2 over the chunk's rows, then E = C Lh^-T
     const double* G1 = G + (size_t)s * Rp;
     rc = lin_product(c, pt, nqt * Rt, Rt, false, nt, 2.0 * (double)Np * Cm * Rp, G1, -1.0, Cq, Rp,
@@ -1928,10 +1955,7 @@ int gpf_predict_conditioned(gpf_ctx* c, const double* ls, const double* xfit, in
     }
     if (!rc && chi2) *chi2 = hchi;
   }
-  hipStreamSynchronize(st);
-  if (c->prof) harvest(c);
-  ks.trim(knobs);
-  return rc;
+  return posterior_close(c, ks, knobs, rc);
 }
 
 // ---- KMeans subsample (find_len_scales.py:25-47; gpf_kmeans.hip) ----
@@ -2541,127 +2565,73 @@ int gpf_predict_mean(gpf_ctx* c, const double* ls, const double* xfit, const dou
   if (M < 0 || (M > 0 && (!xfit || !hfit || !mu || !sd)) || !ls) return bad_arg(c, "gpf_predict_mean: bad arguments");
   if (int rl = check_ls(c, "gpf_predict_mean", ls, (size_t)c->d)) return rl;
   if (M == 0) return GPF_OK;
-  hipSetDevice(c->device);
-  if (c->K <= 0) c->K = 2;  // (as gpf_predict: the objective grid is not needed)
-  const Knobs knobs = Knobs::from_env();
-  if (int rw = ensure_work(c, 1, knobs)) return rw;
   KeptSet& ks = c->kept[KEPT_PMEAN];
   const int64_t Np = c->Npad;
   const int nt = c->nt, m = c->bm, mp = c->bmpad;
   const int pieces = (nt + PMEAN_PER - 1) / PMEAN_PER;
-  int64_t chunk = std::min<int64_t>(std::max<int64_t>(std::max<int64_t>(batch, 1), 16384), M);
-  int64_t Cp = ((chunk + T - 1) / T) * T;
-  SetPlan p = pmean_plan(c, Cp);
-  if (!ks.fits(p.bytes, PMEAN_NBUF)) {
-    Budget bg;
-    if (int rb = half_free(c, nullptr, &bg)) return rb;
-    const int64_t per_col = (Np + 2 * nt + T + mp + (int64_t)pieces * T) * 8;
-    const int64_t maxcols = std::max<int64_t>(T, (int64_t)(bg.half / (double)per_col));
-    chunk = std::min<int64_t>(chunk, maxcols);
-    Cp = ((chunk + T - 1) / T) * T;
-    p = pmean_plan(c, Cp);
-    if (!ks.fits(p.bytes, PMEAN_NBUF))
-      if (int rg = ks.regrow(c, p.bytes, PMEAN_PINNED, PMEAN_NBUF)) return rg;
-  }
-  double *d_xf = ks.as(PRED_XF), *d_ks = ks.as(PRED_KS), *d_vsq = ks.as(PRED_VSQ), *d_vz = ks.as(PRED_VZ);
-  double *d_mu = ks.as(PRED_MU), *d_sd = ks.as(PRED_SD), *hx = ks.as(PRED_HX), *hout = ks.as(PRED_HOUT);
-  double *d_hf = ks.as(PMEAN_HF), *d_bt = ks.as(PMEAN_BT), *d_kb = ks.as(PMEAN_KB), *d_part = ks.as(PMEAN_PART);
-  double* hh = ks.as(PMEAN_HH);
-  const MeanBufs b(ks.as(PMEAN_W), 1, (size_t)Np, (size_t)mp);
-  auto stage_chunk = [&](int64_t s0, int64_t mq) -> int {
-    for (int k = 0; k < c->d; ++k) std::memcpy(hx + (size_t)k * Cp, xfit + (size_t)k * M + s0, (size_t)mq * 8);
-    for (int r = 0; r < m; ++r) std::memcpy(hh + (size_t)r * Cp, hfit + (size_t)r * M + s0, (size_t)mq * 8);
-    GPF_HIP(c, hipMemcpyAsync(d_xf, hx, (size_t)c->d * Cp * 8, hipMemcpyHostToDevice, c->stream));
-    GPF_HIP(c, hipMemcpyAsync(d_hf, hh, (size_t)m * Cp * 8, hipMemcpyHostToDevice, c->stream));
+  auto bufs = [&] { return MeanBufs(ks.as(PMEAN_W), 1, (size_t)Np, (size_t)mp); };
+  std::vector<double> hsmall(gpf::MV_N + 2 * gpf::MEAN_MAX);               // out | t | beta of slot 0
+  std::vector<double> inv(bcov ? (size_t)gpf::MEAN_MAX * gpf::MEAN_MAX : 0);  // k_mean_small's Lai = La^-1
+  Prediction q{"gpf_predict_mean", KEPT_PMEAN, pmean_plan, PMEAN_NBUF, PMEAN_PINNED,
+               (Np + 2 * nt + T + mp + (int64_t)pieces * T) * 8, ls, xfit, M, batch, mu, sd};
+  q.rows = hfit;
+  q.nrows = m;
+  q.rows_host = PMEAN_HH;
+  q.rows_dev = PMEAN_HF;
+  q.before_factor = [&]() -> int {
+    const double ones[2] = {1.0, 1.0};  // the unit model: (a, s) go through the data (gpfit.amplitude.scaled_data)
+    GPF_HIP(c, hipMemcpyAsync(bufs().as, ones, 16, hipMemcpyHostToDevice, c->stream));
+    GPF_HIP(c, hipMemsetAsync(ks.as(PMEAN_BT), 0, (size_t)Np * T * 8, c->stream));
     return GPF_OK;
   };
-  std::memcpy(c->h_ls, ls, (size_t)c->d * 8);
-  GPF_HIP(c, hipMemcpyAsync(c->d_ls, c->h_ls, (size_t)c->d * 8, hipMemcpyHostToDevice, c->stream));
-  int rc = stage_chunk(0, std::min<int64_t>(chunk, M));
-  if (rc) return rc;
-  const double ones[2] = {1.0, 1.0};  // the unit model: (a, s) go through the data (gpfit.amplitude.scaled_data)
-  GPF_HIP(c, hipMemcpyAsync(b.as, ones, 16, hipMemcpyHostToDevice, c->stream));
-  GPF_HIP(c, hipMemsetAsync(d_bt, 0, (size_t)Np * T * 8, c->stream));
-  rc = factor_single_async(c, nullptr, nullptr, knobs);
-  if (rc) return rc;
   // Zo, t, beta, La and zr of slot 0, then Bt^T into the 128-wide operand
-  if ((rc = mean_enqueue_small(c, 1, b))) return rc;
-  if ((rc = mean_enqueue_tn(c, 1, b, d_bt, nullptr, 0, 1, T))) return rc;
-  std::vector<double> hsmall(gpf::MV_N + 2 * gpf::MEAN_MAX);  // out | t | beta of slot 0
-  for (int64_t s = 0; s < M && rc == GPF_OK; s += chunk) {
-    const int64_t mq = std::min<int64_t>(chunk, M - s);
+  q.after_factor = [&] {
+    const int rc = mean_enqueue_small(c, 1, bufs());
+    return rc ? rc : mean_enqueue_tn(c, 1, bufs(), ks.as(PMEAN_BT), nullptr, 0, 1, T);
+  };
+  q.z = [&] { return (const double*)bufs().zr; };  // K_s^T at and sum v^2: gpf_predict's kernel with zr in z's place
+  q.out = [&](int64_t s, int64_t mq, int64_t Cp) -> int {
     const int nqt = (int)((mq + T - 1) / T);
-    const int Cm = nqt * T;
-    if (s > 0) {
-      if (hipStreamSynchronize(c->stream) != hipSuccess) {  // the staging buffers are reused
-        rc = GPF_HIP_ERROR;
-        break;
-      }
-      if ((rc = stage_chunk(s, mq))) break;
-    }
-    rc = launch(c, PC_PREDK, 8.0 * Np * Cm, [&] {
-      gpf::launch_cross_cov(c->stream, (int)c->N, (int)mq, (int)Np, Cm, c->d, c->d_x, (int)c->N, d_xf, (int)Cp, c->d_ls,
-                            d_ks, (int64_t)Cp);
-    });
-    if (rc) break;
-    // K_s^T at and sum v^2: gpf_predict's kernel with zr in z's place
-    const double vflops = 2.0 * T * T * (double)Cm * ((double)nt * (nt + 1) / 2) - (double)T * T * Cm * nt;
-    rc = launch(c, PC_PRED, vflops, [&] {
-      hipLaunchKernelGGL(gpf::k_predict_vsq, dim3(nqt, nt), dim3(gpf::Geo<T>::NTH), 0, c->stream, (int)Np, c->d_U, d_ks,
-                         (int)Cp, d_vsq, b.zr, d_vz, 0);
-    });
-    if (rc) break;
+    const MeanBufs b = bufs();
     // K_s^T Bt^T over fixed depth pieces, added in piece order
-    rc = launch(c, PC_PRED, 2.0 * (double)Np * Cm * T, [&] {
+    int rc = launch(c, PC_PRED, 2.0 * (double)Np * nqt * T * T, [&] {
       hipLaunchKernelGGL(gpf::k_con_tn, dim3((unsigned)nqt, (unsigned)pieces), dim3(gpf::Geo<T>::NTH), 0, c->stream, 1, nt,
-                         PMEAN_PER, 0, d_ks, (int)Cp, d_bt, T, d_part);
-      hipLaunchKernelGGL(gpf::k_lin_reduce, dim3((unsigned)nqt, 8), dim3(NTHR), 0, c->stream, 1, 0, pieces, d_part,
-                         (const double*)nullptr, 1.0, d_kb, (int64_t)T);
+                         PMEAN_PER, 0, ks.as(PRED_KS), (int)Cp, ks.as(PMEAN_BT), T, ks.as(PMEAN_PART));
+      hipLaunchKernelGGL(gpf::k_lin_reduce, dim3((unsigned)nqt, 8), dim3(NTHR), 0, c->stream, 1, 0, pieces, ks.as(PMEAN_PART),
+                         (const double*)nullptr, 1.0, ks.as(PMEAN_KB), (int64_t)T);
     });
-    if (rc) break;
+    if (rc) return rc;
     rc = launch(c, PC_LOSS, 0.0, [&] {
-      hipLaunchKernelGGL(gpf::k_mean_out, dim3((unsigned)((mq + NTHR - 1) / NTHR)), dim3(NTHR), 0, c->stream, nt, (int)mq, m, d_vz,
-                         (int)Cp, d_vsq, d_hf, d_kb, T, b.La, b.beta, d_mu, d_sd);
+      hipLaunchKernelGGL(gpf::k_mean_out, dim3((unsigned)((mq + NTHR - 1) / NTHR)), dim3(NTHR), 0, c->stream, nt, (int)mq, m,
+                         ks.as(PRED_VZ), (int)Cp, ks.as(PRED_VSQ), ks.as(PMEAN_HF), ks.as(PMEAN_KB), T, b.La, b.beta,
+                         ks.as(PRED_MU), ks.as(PRED_SD));
     });
-    if (rc) break;
-    if (hipMemcpyAsync(hout, d_mu, (size_t)mq * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-        hipMemcpyAsync(hout + Cp, d_sd, (size_t)mq * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-        (s == 0 && hipMemcpyAsync(hsmall.data(), b.out, hsmall.size() * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
-        hipStreamSynchronize(c->stream) != hipSuccess) {
+    if (!rc && s == 0 && hipMemcpyAsync(hsmall.data(), b.out, hsmall.size() * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
       rc = GPF_HIP_ERROR;
       c->err = "gpf_predict_mean: copy back failed";
-      break;
     }
-    if (s == 0) {  // the factorisation's status and At's, before anything reaches the caller's buffers
-      rc = particle_status(c, 0);
-      if (!rc && hsmall[gpf::MV_BAD] != 0.0) {
-        c->err = "H Kt^-1 H^T is not positive definite (the basis is rank-deficient at these length scales)";
-        rc = GPF_NOT_PD;
+    return rc;
+  };
+  q.first_check = [&]() -> int {  // At's status; the stream is idle: La for cov(beta) while the set is held
+    if (hsmall[gpf::MV_BAD] != 0.0) {
+      c->err = "H Kt^-1 H^T is not positive definite (the basis is rank-deficient at these length scales)";
+      return GPF_NOT_PD;
+    }
+    if (bcov) GPF_HIP(c, hipMemcpy(inv.data(), bufs().La, inv.size() * 8, hipMemcpyDeviceToHost));
+    return GPF_OK;
+  };
+  const int rc = predict_chunks(c, q);
+  if (rc) return rc;
+  // out | t | beta lie behind one another in MeanBufs: beta from the copy of chunk 0
+  if (beta) std::memcpy(beta, hsmall.data() + gpf::MV_N + gpf::MEAN_MAX, (size_t)m * 8);
+  if (bcov)  // cov(beta) = At^-1 = Lai^T Lai (m <= 32: on the host)
+    for (int i = 0; i < m; ++i)
+      for (int j = 0; j < m; ++j) {
+        double v = 0.0;
+        for (int k = std::max(i, j); k < m; ++k) v += inv[(size_t)k * gpf::MEAN_MAX + i] * inv[(size_t)k * gpf::MEAN_MAX + j];
+        bcov[(size_t)i * m + j] = v;
       }
-      if (rc) break;
-    }
-    std::memcpy(mu + s, hout, (size_t)mq * 8);
-    std::memcpy(sd + s, hout + Cp, (size_t)mq * 8);
-  }
-  hipStreamSynchronize(c->stream);
-  if (c->prof) harvest(c);
-  if (rc == GPF_OK) {
-    // out | t | beta lie behind one another in MeanBufs: beta from the copy of chunk 0
-    const double* hbeta = hsmall.data() + gpf::MV_N + gpf::MEAN_MAX;
-    if (beta) std::memcpy(beta, hbeta, (size_t)m * 8);
-    if (bcov) {  // cov(beta) = At^-1 = Lai^T Lai from k_mean_small's Lai = La^-1 (m <= 32: on the host)
-      std::vector<double> inv((size_t)gpf::MEAN_MAX * gpf::MEAN_MAX);
-      GPF_HIP(c, hipMemcpy(inv.data(), b.La, inv.size() * 8, hipMemcpyDeviceToHost));
-      for (int i = 0; i < m; ++i)
-        for (int j = 0; j < m; ++j) {
-          double v = 0.0;
-          for (int k = std::max(i, j); k < m; ++k) v += inv[(size_t)k * gpf::MEAN_MAX + i] * inv[(size_t)k * gpf::MEAN_MAX + j];
-          bcov[(size_t)i * m + j] = v;
-        }
-    }
-  }
-  ks.trim(knobs);
-  return rc;
+  return GPF_OK;
 }
 
 // ---- gpf_predict_batch: prediction for a batch of length-scale samples and their mixture ----
@@ -2794,9 +2764,8 @@ int gpf_predict_batch(gpf_ctx* c, const double* ls, int P, const double* w, cons
     for (int p = 0; p < P; ++p) wn[p] = w[p] / sum;
   }
   if (P == 0 || M == 0) return GPF_OK;
-  hipSetDevice(c->device);
-  if (c->K <= 0) c->K = 2;  // as gpf_predict: the histogram is sized minimally
-  const Knobs knobs = Knobs::from_env();
+  Knobs knobs;
+  posterior_open(c, 0, &knobs);  // (the workspace below, once the plan has sized it)
   const int64_t N = c->N, Np = c->Npad, Mp = ((M + T - 1) / T) * T;
   const bool each = mu_PM || sd_PM;
   PbatchPlan plan;
@@ -2860,8 +2829,7 @@ int gpf_predict_batch(gpf_ctx* c, const double* ls, int P, const double* w, cons
                                 c->d_ls + (size_t)q * d, d_ks + (size_t)q * Np * Cq, Cq);
       });
       if (rc) break;
-      const double vflops = 2.0 * T * T * (double)Cm * ((double)nt * (nt + 1) / 2) - (double)T * T * Cm * nt;
-      rc = launch(c, PC_PRED, vflops * pc, [&] {
+      rc = launch(c, PC_PRED, v_flops(nt, Cm) * pc, [&] {
         hipLaunchKernelGGL(gpf::k_predict_vsq_batch, order ? dim3(nqt, pc, nt) : dim3(nqt, nt, pc), dim3(gpf::Geo<T>::NTH), 0,
                            c->stream, (int)Np, nt, c->d_U, d_ks, (int)Cq, (size_t)Np * Cq, d_vsq, c->d_yb, d_vz, order);
       });
@@ -2909,10 +2877,7 @@ int gpf_predict_batch(gpf_ctx* c, const double* ls, int P, const double* w, cons
       c->err = "gpf_predict_batch: copy back failed";
     }
   }
-  hipStreamSynchronize(c->stream);
-  if (c->prof) harvest(c);
-  ks.trim(knobs);
-  return rc;
+  return posterior_close(c, ks, knobs, rc);
 }
 
 // Host-only: gpf_predict_batch's memory plan for given byte counts (no device, no context): see gpfit.h.

@@ -285,6 +285,15 @@ class Context:
         if self.d and ls.shape[0] != self.d:
             raise ValueError(f"lengths must be ({self.d},)")
 
+    def _lengths_and_queries(self, lengths, x_fit):
+        """(ls (d,), xf (d, M)) of a posterior call as contiguous float64 arrays; ValueError otherwise."""
+        ls, xf = _f64(lengths).reshape(-1), _f64(x_fit)
+        if xf.ndim != 2:
+            raise ValueError("x_fit must be (d, M)")
+        if self.d and (xf.shape[0] != self.d or ls.shape[0] != self.d):
+            raise ValueError(f"x_fit must be ({self.d}, M) and lengths ({self.d},)")
+        return ls, xf
+
     def eval_batch(self, positions, want_mu_sd=False):
         P = _f64(positions)
         if P.ndim == 1:
@@ -320,12 +329,7 @@ class Context:
         self._check(self.lib.gpf_sync(self._h), "gpf_sync")
 
     def predict(self, lengths, x_fit, batch_size=10000):
-        ls = _f64(lengths).reshape(-1)
-        xf = _f64(x_fit)
-        if xf.ndim != 2:
-            raise ValueError("x_fit must be (d, M)")
-        if self.d and (xf.shape[0] != self.d or ls.shape[0] != self.d):
-            raise ValueError(f"x_fit must be ({self.d}, M) and lengths ({self.d},)")
+        ls, xf = self._lengths_and_queries(lengths, x_fit)
         m = xf.shape[1]
         mu, sd = np.empty(m), np.empty(m)
         self._check(self.lib.gpf_predict(self._h, _ptr(ls), _ptr(xf), m, int(batch_size), _ptr(mu), _ptr(sd)),
@@ -338,12 +342,7 @@ class Context:
         diagonal; mu is bitwise predict()'s. LinAlgError if the covariance of the training points
         is not positive definite, ValueError for bad arguments or an M whose dense cov does not
         fit the device (the message names the largest M that does)."""
-        ls = _f64(lengths).reshape(-1)
-        xf = _f64(x_fit)
-        if xf.ndim != 2:
-            raise ValueError("x_fit must be (d, M)")
-        if self.d and (xf.shape[0] != self.d or ls.shape[0] != self.d):
-            raise ValueError(f"x_fit must be ({self.d}, M) and lengths ({self.d},)")
+        ls, xf = self._lengths_and_queries(lengths, x_fit)
         m = xf.shape[1]
         mu, cov = np.empty(m), np.empty((m, m))
         self._check(self.lib.gpf_predict_cov(self._h, _ptr(ls), _ptr(xf), m, _ptr(mu), _ptr(cov)), "gpf_predict_cov")
@@ -358,11 +357,8 @@ class Context:
         chunk gives the same bits on every call; another chunk may differ in the last bits.
         LinAlgError if the covariance of the training points is not positive definite, ValueError for
         bad arguments or an M that does not fit the device at this R (the message names the largest)."""
-        ls, xf, w = _f64(lengths).reshape(-1), _f64(x_fit), _f64(weights)
-        if xf.ndim != 2:
-            raise ValueError("x_fit must be (d, M)")
-        if self.d and (xf.shape[0] != self.d or ls.shape[0] != self.d):
-            raise ValueError(f"x_fit must be ({self.d}, M) and lengths ({self.d},)")
+        ls, xf = self._lengths_and_queries(lengths, x_fit)
+        w = _f64(weights)
         m = xf.shape[1]
         if w.ndim != 2 or w.shape[1] != m:
             raise ValueError(f"weights must be (R, {m})")
@@ -384,12 +380,8 @@ class Context:
         bitwise predict_linear()'s at the same chunk. ``chunk`` as predict_linear. With R = 0 the
         plain prediction. LinAlgError if the covariance of the training points or H is not positive
         definite (redundant functionals with zero noise), ValueError for bad arguments."""
-        ls, xf, w = _f64(lengths).reshape(-1), _f64(x_fit), _f64(weights)
-        b, s = _f64(values).reshape(-1), _f64(noise).reshape(-1)
-        if xf.ndim != 2:
-            raise ValueError("x_fit must be (d, M)")
-        if self.d and (xf.shape[0] != self.d or ls.shape[0] != self.d):
-            raise ValueError(f"x_fit must be ({self.d}, M) and lengths ({self.d},)")
+        ls, xf = self._lengths_and_queries(lengths, x_fit)
+        w, b, s = _f64(weights), _f64(values).reshape(-1), _f64(noise).reshape(-1)
         m = xf.shape[1]
         if w.ndim != 2 or w.shape[1] != m:
             raise ValueError(f"weights must be (R, {m})")
@@ -603,12 +595,8 @@ class Context:
         """predict with the mean function of set_basis (gpf_predict_mean, the unit model a = s = 1):
         (mu (M,), sd (M,)) at x_fit (d, M) with h_fit (m, M) the basis there; sd includes the share of
         not knowing the coefficients. With want_beta also (beta (m,), cov(beta) (m, m))."""
-        ls = _f64(lengths).reshape(-1)
-        xf, hf = _f64(x_fit), _f64(h_fit)
-        if xf.ndim != 2:
-            raise ValueError("x_fit must be (d, M)")
-        if self.d and (xf.shape[0] != self.d or ls.shape[0] != self.d):
-            raise ValueError(f"x_fit must be ({self.d}, M) and lengths ({self.d},)")
+        ls, xf = self._lengths_and_queries(lengths, x_fit)
+        hf = _f64(h_fit)
         if self.N and not self.m:
             raise ValueError("predict_mean: no basis for this data: call set_basis after set_data")
         if hf.ndim == 1:

@@ -297,6 +297,37 @@ def test_not_positive_definite_raises_like_numpy(ctx):
         GP_func.GP(x, y, e, x, np.array([1.0]))
 
 
+def test_predict_not_positive_definite_leaves_outputs_untouched(ctx):
+    """test_predict_cov_gpu.py's recipe for gpf_predict: N = 128, d = 1, M = 128, the first two training
+    points identical with e = 0 (K's leading 2x2 block is exactly [[1, 1], [1, 1]] and the second
+    pivot exactly 0). GPF_NOT_PD from the raw entry point, the caller's buffers untouched, and the next
+    call on the good data is within the module's tolerance of the oracle."""
+    import ctypes
+    import gpfit._lib as L
+    from test_predict_cov_gpu import _case
+    x, y, e, ls, q = _case(128, 1, 128)
+    xb, eb = x.copy(), e.copy()
+    xb[:, 1] = xb[:, 0]
+    eb[:2] = 0.0
+    with pytest.raises(np.linalg.LinAlgError):
+        ref_cpu.GP(xb, y, eb, q, ls[0])
+    ctx.set_data(xb, y, eb)
+    with pytest.raises(np.linalg.LinAlgError, match="Matrix is not positive definite"):
+        ctx.predict(ls[0], q)
+    M = q.shape[1]
+    mu, sd = np.full(M, -7.25), np.full(M, -7.25)
+    l0, qc = np.ascontiguousarray(ls[0]), np.ascontiguousarray(q)
+    dp = ctypes.POINTER(ctypes.c_double)
+    rc = ctx.lib.gpf_predict(ctx._h, l0.ctypes.data_as(dp), qc.ctypes.data_as(dp), M, 10000, mu.ctypes.data_as(dp),
+                             sd.ctypes.data_as(dp))
+    assert rc == L.GPF_NOT_PD
+    assert np.all(mu == -7.25) and np.all(sd == -7.25)
+    ctx.set_data(x, y, e)
+    mu, sd = ctx.predict(ls[0], q)
+    m0, s0 = ref_cpu.GP(x, y, e, q, ls[0])
+    assert _rel(mu, m0) < RTOL_MU_SD and _rel(sd, s0) < RTOL_MU_SD
+
+
 def _cluster_data(N, c0, nc=20, spacing=0.01, dup=False):
     """d = 1 points where K's first failing pivot sits past row 384 for a chosen particle only:
     x_i = i (unit spacing), except a cluster of nc points spaced `spacing` at rows c0.. 50 below the

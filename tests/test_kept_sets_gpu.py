@@ -9,8 +9,13 @@ pytestmark = pytest.mark.gpu
 N, D, R, S, P = 200, 2, 3, 5, 3  # two row tiles, the last one ragged
 
 
+def _basis(x):
+    """The constant + linear basis at the points x (d, m): the rows 1, x_1 .. x_d."""
+    return np.vstack([np.ones(x.shape[1]), x])
+
+
 def _inputs(rng, m):
-    """One call's arguments for each of the eight entry points at width m (query points, rows of the
+    """One call's arguments for each of the nine entry points at width m (query points, rows of the
     probability surface and the dense matrix's order alike)."""
     b = rng.standard_normal((m, m))
     tails = np.empty((m, 4 if m < 200 else 8))
@@ -56,6 +61,7 @@ def _calls(ctx, ls, lsP, a):
         "predict_linear": lambda: ctx.predict_linear(ls, a["xf"], a["w"], want_prior=True),
         "predict_conditioned": conditioned,
         "predict_batch": batch,
+        "predict_mean": lambda: ctx.predict_mean(ls, a["xf"], _basis(a["xf"]), want_beta=True),
         "chol_dense": dense,
         "prob_surface": psurf,
     }
@@ -63,7 +69,7 @@ def _calls(ctx, ls, lsP, a):
 
 @pytest.mark.parametrize("keep_mb", [None, "0"])
 def test_kept_sets_are_independent(monkeypatch, keep_mb):
-    """All eight entry points at M = 130 (the first values), at M = 300 in another order, at M = 130
+    """All nine entry points at M = 130 (the first values), at M = 300 in another order, at M = 130
     again, after set_data with N = 300 (the workspace regrows and releases every set) and back on the
     first data at M = 130 once more: every M = 130 output is bitwise its first value, with the sets kept
     (GPF_PREDICT_KEEP_MB unset) and given back after every call (= 0)."""
@@ -83,6 +89,7 @@ def test_kept_sets_are_independent(monkeypatch, keep_mb):
     ctx = gpfit.Context(0)
     try:
         ctx.set_data(*first)
+        ctx.set_basis(_basis(first[0]))
         small, wide = _calls(ctx, ls, lsP, _inputs(rng, 130)), _calls(ctx, ls, lsP, _inputs(rng, 300))
         names = list(small)
         want = {k: small[k]() for k in names}
@@ -98,6 +105,7 @@ def test_kept_sets_are_independent(monkeypatch, keep_mb):
         ctx.set_data(*other)
         ctx.predict(ls, other[0][:, :130])  # ensure_work regrows the workspace for the new N
         ctx.set_data(*first)
+        ctx.set_basis(_basis(first[0]))  # (set_data with other data discarded it)
         check(names[::2] + names[1::2], "after other training data")
     finally:
         ctx.close()
