@@ -16,7 +16,9 @@ mle_num_starts (40) and hyper_samples (K >= 1: the written mean and sd are margi
 length-scale samples, gpfit.hyper.predict_marginal, instead of taken at the one fitted vector; it
 reuses pso_max_points and pso_seed) and mean_function ("constant", "linear" or "quadratic": a polynomial
 mean with its coefficients integrated out, gpfit.meanfn.fit_mean and GP_mean; valid only with
-len_scale_objective: marginal_likelihood_full).
+len_scale_objective: marginal_likelihood_full) and kernel ("se", "matern32" or "matern52": the covariance
+kernel of the fit and of the prediction, gpfit.kernels; it combines with every len_scale_objective, with
+hyper_samples and with mean_function).
 """
 from functools import reduce
 from pathlib import Path
@@ -26,7 +28,7 @@ import yaml
 
 from convex_hull import fill_convex_hull
 from find_len_scales import len_scale_opt
-from GP_func import GP, GP_hyper, GP_mean
+from GP_func import GP, GP_hyper, GP_kernel, GP_mean
 from read_in import read_yaml
 
 __all__ = ["process_experiment", "write_individual_file", "write_grouped_file", "write_combined_file",
@@ -81,12 +83,28 @@ def _mean_function(options_path="options.yaml"):
     return kind
 
 
+def _kernel(options_path="options.yaml"):
+    """options.yaml's kernel ("se", "matern32" or "matern52"), or None (absent: the squared-exponential
+    model through exactly the calls made without the key, byte-identical outputs)."""
+    try:
+        with open(options_path, "r") as f:
+            opts = yaml.safe_load(f) or {}
+    except OSError:
+        return None
+    kernel = opts.get("kernel")
+    if kernel is None:
+        return None
+    if not isinstance(kernel, str) or kernel not in ("se", "matern32", "matern52"):
+        raise ValueError(f"options.yaml: kernel must be se, matern32 or matern52, not {kernel!r}")
+    return kernel
+
+
 def _marginal(x_known, y_known, e_known, x_fit, ls, k, pso):
     """predict_marginal's mean and sd at K samples around the marginal likelihood's optimum: the fitted
     vector when the fit maximised it, else gpfit.mle.fit_lml's (the swarm's optimum of the calibration
     loss is not the centre of the likelihood)."""
     from gpfit.hyper import predict_marginal
-    kw = {key: pso[key] for key in ("max_points", "seed") if key in pso}
+    kw = {key: pso[key] for key in ("max_points", "seed", "kernel") if key in pso}
     best = ls if pso.get("objective") == "marginal_likelihood" else None
     mu, sd, _ = predict_marginal(x_known, y_known, e_known, x_fit, best_l=best, n_samples=k, **kw)
     return mu, sd
@@ -96,7 +114,7 @@ def _fit_full(x_known, y_known, e_known, progress, pso, mean_function=None):
     """theta = (l.., a, s) of len_scale_objective: marginal_likelihood_full (gpfit.amplitude.fit_hyper;
     with a mean function gpfit.meanfn.fit_mean)."""
     import numpy as np
-    kw = {key: pso[key] for key in ("num_starts", "max_points", "seed") if key in pso}
+    kw = {key: pso[key] for key in ("num_starts", "max_points", "seed", "kernel") if key in pso}
     data = (np.asarray(x_known, dtype=np.float64), np.asarray(y_known, dtype=np.float64),
             np.asarray(e_known, dtype=np.float64))
     if mean_function is not None:
@@ -114,7 +132,8 @@ def _merge(frames, on):
 def process_experiment(x_known, y_known, e_known, resolution, dim_labels, filename, exp_idx, total_exps,
                        PSO_progress, hyper_samples=None, mean_function=None, **pso):
     """Length scales by PSO, hull grid, GP prediction -> DataFrame (GP_fit.py:20-46). hyper_samples=K
-    writes the prediction marginalised over K length-scale samples instead of GP's."""
+    writes the prediction marginalised over K length-scale samples instead of GP's. A ``kernel`` in pso
+    (options.yaml's, absent for the default) is the covariance kernel of the fit and of the prediction."""
     if x_known.shape[1] == 0:
         print("  Skipping experiment: no valid data points")
         return None
@@ -129,10 +148,13 @@ def process_experiment(x_known, y_known, e_known, resolution, dim_labels, filena
     else:
         ls = len_scale_opt(x_known, y_known, e_known, PSO_progress, **pso)
     grid = fill_convex_hull(x_known.T, resolution)
+    kkw = {"kernel": pso["kernel"]} if "kernel" in pso else {}
     if full and mean_function is not None:
-        mu, sd = GP_mean(x_known, y_known, e_known, grid.T, ls, mean_function)
+        mu, sd = GP_mean(x_known, y_known, e_known, grid.T, ls, mean_function, **kkw)
     elif full:
-        mu, sd = GP_hyper(x_known, y_known, e_known, grid.T, ls)
+        mu, sd = GP_hyper(x_known, y_known, e_known, grid.T, ls, **kkw)
+    elif hyper_samples is None and kkw:
+        mu, sd = GP_kernel(x_known, y_known, e_known, grid.T, ls, pso["kernel"])
     elif hyper_samples is None:
         mu, sd = GP(x_known, y_known, e_known, grid.T, ls)
     else:
@@ -193,6 +215,9 @@ def create_GP():
     mean_function = _mean_function()
     if mean_function is not None:
         pso = dict(pso, mean_function=mean_function)
+    kernel = _kernel()
+    if kernel is not None:
+        pso = dict(pso, kernel=kernel)
     nd = len(resolution)
     dim_labels = labels[:nd]
     out_path = Path(out_name) if out_name else Path("GP_results.txt")

@@ -1,13 +1,14 @@
-// gpf_covariance.hip — squared-exponential covariance builders (HBM-bound writes).
+// gpf_covariance.hip — covariance builders (HBM-bound writes) for the context's kernel (gpf_covfn.hip).
 //
 // kernel_func (GP_func.py:49-65): a = x / l per dimension (:56-57), squared norms
 // summed over dimensions in order (:59-60), (|a_i|^2 + |a_j|^2) - 2 a_i.a_j (:62),
-// clamp at 0 (:63), exp(-0.5 r2) (:65); K adds diag(e^2) (:21). One 64x64 output
+// clamp at 0 (:63), exp(-0.5 r2) (:65; cov_value<KIND>(r2) in general); K adds diag(e^2) (:21). One 64x64 output
 // tile per workgroup: the scaled coordinates of its 64 rows and 64 columns are
 // staged in LDS once, then every lane writes 16 outputs, consecutive lanes on
 // consecutive columns (512 contiguous bytes per row per wave).
 #pragma once
 #include "gpf_common.hip"
+#include "gpf_covfn.hip"
 
 namespace gpf {
 
@@ -24,6 +25,7 @@ constexpr int BT = 64;  // covariance build tile
 // grid: (nb*(nb+1)/2, P) for every lower 64x64 tile, or (3*nt, P) with diag_only: the lower
 // tiles of the 128-wide diagonal blocks only (k_step computes the others itself).
 // ----------------------------------------------------------------------------
+template <int KIND = COV_SE>
 __global__ __launch_bounds__(NTHR) void k_build_cov(int N, int Npad, int d, const double* __restrict__ x,
                                                     const double* __restrict__ y, const double* __restrict__ e,
                                                     const double* __restrict__ ls, double* __restrict__ Lb,
@@ -95,7 +97,7 @@ __global__ __launch_bounds__(NTHR) void k_build_cov(int N, int Npad, int d, cons
       for (int k = 1; k < d; ++k) dot = fma(ai[k][r], aj[k][c], dot);
       double r2 = (ni[r] + nj[c]) - 2.0 * dot;
       r2 = r2 > 0.0 ? r2 : 0.0;  // np.maximum(sq_dist, 0)
-      v = exp(-0.5 * r2);
+      v = cov_value<KIND>(r2);
       if (gi == gj) v = v + (e[gi] * nf) * e[gi];
     } else {
       v = (gi == gj) ? 1.0 : 0.0;
@@ -123,7 +125,7 @@ constexpr int CC_R = 32, CC_C = 256;
 __host__ __device__ constexpr size_t cross_cov_lds(int d) { return (size_t)(d + 1) * (CC_R + CC_C) * 8; }
 // The block (blockIdx.y, blockIdx.x) of the output: the body of k_cross_cov and, with a particle's
 // l and out, of k_cross_cov_batch (gpf_predbatch.hip).
-template <int D>
+template <int D, int KIND = COV_SE>
 __device__ __forceinline__ void cross_cov_block(int N1, int N2, int R, int C, int dd, const double* __restrict__ x1,
                                                 int ld1, const double* __restrict__ x2, int ld2,
                                                 const double* __restrict__ l, double* __restrict__ out, int64_t ldo) {
@@ -178,19 +180,19 @@ __device__ __forceinline__ void cross_cov_block(int N1, int N2, int R, int C, in
         if (k < d) dot = fma(ai[k * CC_R + r], bc[k], dot);
       double r2 = (ni[r] + nc) - 2.0 * dot;
       r2 = r2 > 0.0 ? r2 : 0.0;
-      v = exp(-0.5 * r2);
+      v = cov_value<KIND>(r2);
     }
     __builtin_nontemporal_store(v, op + (size_t)gi * ldo);
   }
 }
 
-template <int D>
+template <int D, int KIND = COV_SE>
 __global__ __launch_bounds__(NTHR) void k_cross_cov(int N1, int N2, int R, int C, int dd,
                                                     const double* __restrict__ x1, int ld1,
                                                     const double* __restrict__ x2, int ld2,
                                                     const double* __restrict__ l, double* __restrict__ out,
                                                     int64_t ldo) {
-  cross_cov_block<D>(N1, N2, R, C, dd, x1, ld1, x2, ld2, l, out, ldo);
+  cross_cov_block<D, KIND>(N1, N2, R, C, dd, x1, ld1, x2, ld2, l, out, ldo);
 }
 
 // The run-time dimension d as the kernels' template constant: f(std::integral_constant<int, D>) with
@@ -212,12 +214,14 @@ inline void with_cross_cov_dim(int d, F f) {
 // store path; and an exp with the libm's algorithm and constants but one v_fma_f64 per Horner step
 // (28 instead of ~45 VALU instructions per output, bitwise the libm's) was 10-20% slower, its loop
 // no longer unrolled; profiles/r4/ab_cross_cov_pair.txt.)
-inline void launch_cross_cov(hipStream_t stream, int N1, int N2, int R, int C, int d, const double* x1, int ld1,
+inline void launch_cross_cov(hipStream_t stream, int kind, int N1, int N2, int R, int C, int d, const double* x1, int ld1,
                              const double* x2, int ld2, const double* l, double* out, int64_t ldo) {
   const dim3 grid((unsigned)((C + CC_C - 1) / CC_C), (unsigned)((R + CC_R - 1) / CC_R));
-  with_cross_cov_dim(d, [&](auto D) {
-    hipLaunchKernelGGL(k_cross_cov<D()>, grid, dim3(NTHR), cross_cov_lds(d), stream, N1, N2, R, C, d, x1, ld1, x2, ld2, l, out,
-                       ldo);
+  with_cov_kind(kind, [&](auto KIND) {
+    with_cross_cov_dim(d, [&](auto D) {
+      hipLaunchKernelGGL((k_cross_cov<D(), KIND()>), grid, dim3(NTHR), cross_cov_lds(d), stream, N1, N2, R, C, d, x1, ld1, x2, ld2,
+                         l, out, ldo);
+    });
   });
 }
 

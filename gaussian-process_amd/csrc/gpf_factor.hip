@@ -23,6 +23,7 @@
 
 #pragma once
 #include "gpf_common.hip"
+#include "gpf_covfn.hip"
 #include "gpf_diag.hip"
 
 namespace gpf {
@@ -388,7 +389,7 @@ __device__ __forceinline__ unsigned long long realtime() {
 // squared norms of the tile's 128 rows and 128 columns are staged in LDS first. Replaces the
 // write of the K tile in the K build and its read back; only the diagonal blocks are still built
 // (k_build_cov, diag_only).
-template <bool KOUTER = (GPF_COV_KOUTER != 0)>
+template <int KIND = COV_SE, bool KOUTER = (GPF_COV_KOUTER != 0)>
 __device__ __forceinline__ void cov_tile_acc(Acc<T>& acc, const Quad<T>& qd, const double* __restrict__ x,
                                              const double* __restrict__ lp, int d, int N, int R, int C,
                                              double* smem) {
@@ -447,7 +448,7 @@ __device__ __forceinline__ void cov_tile_acc(Acc<T>& acc, const Quad<T>& qd, con
         const int row = qd.row(mi, r);
         double r2 = (na[row] + nc) - 2.0 * acc.v[mi][0][r];
         r2 = r2 > 0.0 ? r2 : 0.0;  // np.maximum(sq_dist, 0)
-        acc.v[mi][0][r] = (cin && R * T + row < N) ? exp(-0.5 * r2) : 0.0;
+        acc.v[mi][0][r] = (cin && R * T + row < N) ? cov_value<KIND>(r2) : 0.0;
         __builtin_amdgcn_sched_barrier(0);  // (one exp at a time: the 32 interleaved spilled)
       }
     __syncthreads();
@@ -466,7 +467,7 @@ __device__ __forceinline__ void cov_tile_acc(Acc<T>& acc, const Quad<T>& qd, con
           for (int k = 1; k < d; ++k) dot = fma(sa[k * T + row], sb[k * T + col], dot);
           double r2 = (na[row] + nb[col]) - 2.0 * dot;
           r2 = r2 > 0.0 ? r2 : 0.0;  // np.maximum(sq_dist, 0)
-          v = exp(-0.5 * r2);
+          v = cov_value<KIND>(r2);
         }
         acc.v[mi][ni][r] = v;
       }
@@ -735,7 +736,7 @@ __device__ __forceinline__ bool flat_syrk_block(double* Aii, size_t ld, const do
 }
 
 // One piece (sidx of np) of tile w of launch J under the flat finish (see above); LT: an L tile.
-template <bool LT>
+template <bool LT, int KIND = COV_SE>
 __device__ __forceinline__ void flat_piece(int J, int w, int p, int nt, int Npad, double* __restrict__ Lp,
                                         double* __restrict__ Up, double* __restrict__ yp, double* __restrict__ s2p,
                                         double* __restrict__ szp, int* __restrict__ info, int N,
@@ -757,7 +758,7 @@ __device__ __forceinline__ void flat_piece(int J, int w, int p, int nt, int Npad
     split_gemm<false, true, true>(acc, Lp + (size_t)J * T * ld, Npad, Lp + (size_t)I * T * ld, Npad, J * T / DL_KC,
                                   np, sidx, lds, qd, [&](Acc<T>& a) {
                                     // (k outer here too: prediction factor -1.8% despite a 20 B private segment, ab_cov_seed_kouter.txt)
-                                    cov_tile_acc<GPF_FLAT_KOUTER != 0>(a, qd, x, lp, d, N, J, I, lds);
+                                    cov_tile_acc<KIND, GPF_FLAT_KOUTER != 0>(a, qd, x, lp, d, N, J, I, lds);
                                   });
   else  // (the triangular first block runs dense: its upper part holds zeros)
     split_gemm<true, false, false>(acc, Lp + (size_t)J * T * ld + (size_t)K * T, Npad,
@@ -940,6 +941,7 @@ __host__ __device__ __forceinline__ int la_chunks(int J) { return 7 * 8 * J / 16
 // another process on the GPU) can never seed from the next tile's partial.
 __host__ __device__ __forceinline__ size_t la_slot(int p, int J) { return (size_t)(2 * p + (J & 1)) * T * T; }
 
+template <int KIND = COV_SE>
 __device__ __forceinline__ void la_item(int J, int p, int Npad, const double* __restrict__ Lb, int N,
                                         const double* __restrict__ x, const double* __restrict__ ls, int d,
                                         double* __restrict__ lab, double* lds) {
@@ -947,7 +949,7 @@ __device__ __forceinline__ void la_item(int J, int p, int Npad, const double* __
   const double* Lp = Lb + (size_t)p * ld * ld;
   const Quad<T> qd;
   Acc<T> acc;
-  cov_tile_acc(acc, qd, x, ls + (size_t)p * d, d, N, J + 1, J + 2, lds);
+  cov_tile_acc<KIND>(acc, qd, x, ls + (size_t)p * d, d, N, J + 1, J + 2, lds);
   gemm_stream_dl<false, true>(acc, Lp + (size_t)(J + 1) * T * ld, Npad, Lp + (size_t)(J + 2) * T * ld, Npad,
                               la_chunks(J) * DL_KC, lds, qd);
   acc.store(qd, lab + la_slot(p, J), T);
@@ -973,6 +975,7 @@ __device__ __forceinline__ void load_node(Acc<T>& acc, const double* slot) {
 // A_{J+1,I}^T (cov_tile_acc) minus L_{J+1,<J} L_{I,<J}^T; U tile K: L_{J+1,[K,J)} U_{[K,J),K} (its first
 // block triangular) — to the particle's slot w' (plain stores: the follow launch reads it after the
 // launch boundary).
+template <int KIND = COV_SE>
 __device__ __forceinline__ void pla_item(int J, int w, int p, int nt, int Npad, const double* __restrict__ Lb,
                                          const double* __restrict__ Ub, int N, const double* __restrict__ x,
                                          const double* __restrict__ ls, int d, double* __restrict__ pb, double* lds) {
@@ -983,7 +986,7 @@ __device__ __forceinline__ void pla_item(int J, int w, int p, int nt, int Npad, 
   Acc<T> acc;
   if (w < nL) {
     const int I = J + 1 + w;
-    cov_tile_acc(acc, qd, x, ls + (size_t)p * d, d, N, J + 1, I, lds);
+    cov_tile_acc<KIND>(acc, qd, x, ls + (size_t)p * d, d, N, J + 1, I, lds);
     gemm_stream_dl<false, true>(acc, Lp + (size_t)(J + 1) * T * ld, Npad, Lp + (size_t)I * T * ld, Npad, J * T, lds, qd);
   } else {
     const int K = w - nL;
@@ -1044,6 +1047,7 @@ __device__ __forceinline__ void lall_seed(Acc<T>& acc, const double* lb, int J, 
 }
 
 // ROLE_LPIECE: piece s of item it of launch J (see lall_items)
+template <int KIND = COV_SE>
 __device__ __forceinline__ void lall_piece(int J, int it, int s, int p, int nt, int Npad, const double* __restrict__ Lb,
                                            const double* __restrict__ Ub, int N, const double* __restrict__ x,
                                            const double* __restrict__ ls, int d, double* __restrict__ lb, int tag,
@@ -1057,7 +1061,7 @@ __device__ __forceinline__ void lall_piece(int J, int it, int s, int p, int nt, 
   Acc<T> acc;
   if (it < nLc) {  // L tile I of column J+1: (A_{J+1,I} seed) - L_{J+1,[b0,b0+nb)} L_{I,[b0,b0+nb)}^T
     const int I = J + 2 + it;
-    if (s == 0) cov_tile_acc(acc, qd, x, ls + (size_t)p * d, d, N, J + 1, I, lds);
+    if (s == 0) cov_tile_acc<KIND>(acc, qd, x, ls + (size_t)p * d, d, N, J + 1, I, lds);
     else acc.zero();
     gemm_stream_dl<false, true>(acc, Lp + (size_t)(J + 1) * T * ld + (size_t)b0 * T, Npad,
                                 Lp + (size_t)I * T * ld + (size_t)b0 * T, Npad, nb * T, lds, qd);
@@ -1111,7 +1115,7 @@ __device__ __forceinline__ void tile_st(double* p, double v) { *p = v; }
 //   U tile (K = w-nL):   W = L_J,[K,J) U_[K,J),K ; U_JK = -U_JJ W (trmm_acc); column partials
 // The products the finishes need never leave the registers: no C or W round trip through
 // memory, no streamed second operand, no barrier inside the triangular multiplies.
-template <int SPLIT, int ED>
+template <int SPLIT, int ED, int KIND = COV_SE>
 __device__ __forceinline__ void step_item(int role, int J, int w, int p, int nt, int Npad, double* __restrict__ Lb,
                                           double* __restrict__ Ub, double* __restrict__ yb,
                                           double* __restrict__ s2p, double* __restrict__ szp,
@@ -1140,10 +1144,10 @@ __device__ __forceinline__ void step_item(int role, int J, int w, int p, int nt,
     // (every tile of the launch: the single-piece ones, ROLE_WHOLE, finish the same way)
     const int np = split_all_pieces(J, w, nt, S);
 if (w < nL)
-      flat_piece<true>(J, w, p, nt, Npad, Lp, Up, yp, s2p, szp, info + p, N, x, ls + (size_t)p * d, d, np, sidx, S2, part,
+      flat_piece<true, KIND>(J, w, p, nt, Npad, Lp, Up, yp, s2p, szp, info + p, N, x, ls + (size_t)p * d, d, np, sidx, S2, part,
                        cnt, sflag, dflag, spins, lds);
     else
-      flat_piece<false>(J, w, p, nt, Npad, Lp, Up, yp, s2p, szp, info + p, N, x, ls + (size_t)p * d, d, np, sidx, S2, part,
+      flat_piece<false, KIND>(J, w, p, nt, Npad, Lp, Up, yp, s2p, szp, info + p, N, x, ls + (size_t)p * d, d, np, sidx, S2, part,
                         cnt, sflag, dflag, spins, lds);
     return;
   }
@@ -1182,7 +1186,7 @@ if (w < nL)
       gemm_stream_dl<false, true>(acc, Lp + (size_t)J * T * ld + (size_t)(J - 1) * T, Npad,
                                   Lp + (size_t)I * T * ld + (size_t)(J - 1) * T, Npad, T, lds, qd);
     } else {
-      cov_tile_acc(acc, qd, x, lp, d, N, J, I, lds);
+      cov_tile_acc<KIND>(acc, qd, x, lp, d, N, J, I, lds);
       if (J > 0)
         gemm_stream_dl<false, true>(acc, Lp + (size_t)J * T * ld, Npad, Lp + (size_t)I * T * ld, Npad, J * T, lds, qd);
     }
@@ -1307,7 +1311,7 @@ if (w < nL)
 // the plain schedule.
 // (SPLIT_ALL's flat finish takes ~110 KiB of LDS: one workgroup per CU, 2 waves per SIMD — the
 // occupancy its register allocation is asked for, instead of an unreachable 4)
-template <int SPLIT, int ED>
+template <int SPLIT, int ED, int KIND = COV_SE>
 __global__ __launch_bounds__(STEP_NTH, SPLIT == SPLIT_ALL ? 2 : STEP_WAVES_PER_SIMD) void k_step(int J, int nt, int Npad, double* __restrict__ Lb,
                                                   double* __restrict__ Ub, double* __restrict__ yb,
                                                   double* __restrict__ s2p, double* __restrict__ szp,
@@ -1381,21 +1385,21 @@ __global__ __launch_bounds__(STEP_NTH, SPLIT == SPLIT_ALL ? 2 : STEP_WAVES_PER_S
 #endif
   if (PAIRS && pair == 1 && pstart) pair_start_sync(J, role == ROLE_SYRK ? 0 : w, uh, p, nt, pstart, ptag);
   if (LALL && role == ROLE_LPIECE) {
-    lall_piece(J, lit, sidx, p, nt, Npad, Lb, Ub, N, x, ls, d, pb, ptag, lds);
+    lall_piece<KIND>(J, lit, sidx, p, nt, Npad, Lb, Ub, N, x, ls, d, pb, ptag, lds);
   } else if (LALL && role == ROLE_SYRK && (pair & 2) && J >= 2) {
     lall_syrk_item(J, p, nt, Npad, Lb, yflag, pb, ptag, lds);
   } else if (PAIRS && role == ROLE_PLA) {
-    pla_item(J, w, p, nt, Npad, Lb, Ub, N, x, ls, d, pb, lds);
+    pla_item<KIND>(J, w, p, nt, Npad, Lb, Ub, N, x, ls, d, pb, lds);
   } else if (PAIRS && role == ROLE_SYRKP) {
     syrkp_item(J, p, Npad, Lb, lds);
   } else if (SPLIT != SPLIT_ALL && role == ROLE_SYRK) {
     syrk_item(J, p, Npad, Lb, yflag, lds);
     if (SPLIT == SPLIT_NONE && ED && (la & 1)) {  // the look-ahead rides on the SYRK workgroup (after its flag)
       __syncthreads();
-      la_item(J, p, Npad, Lb, N, x, ls, d, lab, lds);
+      la_item<KIND>(J, p, Npad, Lb, N, x, ls, d, lab, lds);
     }
   } else if (SPLIT == SPLIT_NONE && ED && role == ROLE_LA) {
-    la_item(J, p, Npad, Lb, N, x, ls, d, lab, lds);
+    la_item<KIND>(J, p, Npad, Lb, N, x, ls, d, lab, lds);
   } else if (ED && role == ROLE_DIAG) {
     // diagonal block J of particle p (fully reduced by the previous launches' look-ahead): factor,
     // then publish to this launch's tiles (write-through stores drained, then the flag)
@@ -1407,7 +1411,7 @@ __global__ __launch_bounds__(STEP_NTH, SPLIT == SPLIT_ALL ? 2 : STEP_WAVES_PER_S
     factor128<true>(Lb + off, Ub + off, ld, yb + (size_t)p * Npad + J * T, s2p + poff, szp + poff, info + p, lds,
                     dflag + p, J);
   } else {
-    step_item<SPLIT, ED>(role, J, w, p, nt, Npad, Lb, Ub, yb, s2p, szp, info, N, x, ls, d, S, S2, sidx, part, cnt, &sflag,
+    step_item<SPLIT, ED, KIND>(role, J, w, p, nt, Npad, Lb, Ub, yb, s2p, szp, info, N, x, ls, d, S, S2, sidx, part, cnt, &sflag,
                          dflag, yflag, defer, spins, la, lab, pair, pb, ptag, lds);
   }
   span.stop(clk);

@@ -1,15 +1,16 @@
 // gpf_lmlgrad.hip — log marginal likelihood and its length-scale gradient for a batch of
 // particles, from what a factorisation leaves on the device (L, U = L^-1, the szp partials of alpha).
 //
-// Fixed amplitude 1, fixed noise e^2, ARD squared-exponential (GP_func.py:49-65). With
-// Kn = kernel_func(x, x, l) + diag(e^2), W = Kn^-1 = U^T U and alpha = W y:
+// Fixed amplitude 1, fixed noise e^2, the context's ARD kernel (gpf_covfn.hip; se: GP_func.py:49-65). With
+// Kn = K(x, x, l) + diag(e^2), W = Kn^-1 = U^T U and alpha = W y:
 //   LML       = -1/2 y^T alpha - sum_i log L_ii - N/2 log(2 pi)
-//   dLML/dl_k = sum_{i>j} (alpha_i alpha_j - W_ij) K_ij (x_ik - x_jk)^2 / l_k^3
-// (K_ij the noise-free kernel value; the diagonal terms vanish and the noise does not depend on l,
-// so only the strict lower triangle is needed). W is never stored: every 128x128 tile of it is
+//   dLML/dl_k = sum_{i>j} (alpha_i alpha_j - W_ij) psi_ij (x_ik - x_jk)^2 / l_k^3
+// (psi_ij = cov_dweight<KIND>(r2_ij): the noise-free kernel value K_ij itself under se; the diagonal
+// terms vanish and the noise does not depend on l, so only the strict lower triangle is needed). W is never stored: every 128x128 tile of it is
 // reduced in registers, as k_predict_vsq reduces V.
 #pragma once
 #include "gpf_common.hip"
+#include "gpf_covfn.hip"
 
 namespace gpf {
 
@@ -74,8 +75,8 @@ static_assert(2 * DMAX * T <= DL_STAGE, "grad_epilogue: the tile's coordinates f
 
 // The epilogue of k_lml_grad and k_loo_grad: acc holds tile (I, J <= I) of a symmetric matrix M for
 // particle p (after a GEMM that ended with a barrier), and for every element j < i < N
-//   w_ij = weight(rows' vectors at i, columns' vectors at j, M_ij) K_ij,
-// K_ij the noise-free kernel value recomputed from x and the particle's length scales lp with
+//   w_ij = weight(rows' vectors at i, columns' vectors at j, M_ij) psi_ij,
+// psi_ij = cov_dweight<KIND>(r2_ij) (under se the noise-free kernel value K_ij) recomputed from x and the particle's length scales lp with
 // k_build_cov's operation order (d_L holds L by now). Then per coordinate k
 //   partial[p][tile][k] = sum_ij w_ij (x_ik - x_jk)^2
 // summed in a fixed order: per lane over its 32 rows (ascending), over the 4 lane groups
@@ -83,7 +84,7 @@ static_assert(2 * DMAX * T <= DL_STAGE, "grad_epilogue: the tile's coordinates f
 // floating-point atomics: the same inputs give the same bits.
 // load(v, g): vector v < NV at point g < N. weight(r, c, m): r[v] and c[v] the vectors at the row and
 // at the column.
-template <int NV, typename Load, typename Weight>
+template <int NV, int KIND = COV_SE, typename Load, typename Weight>
 __device__ __forceinline__ void grad_epilogue(Acc<T>& acc, const Quad<T>& qd, double* smem, int I, int J, int p, int N, int d,
                                               const double* __restrict__ x, const double* __restrict__ lp, Load load,
                                               Weight weight, double* __restrict__ partial) {
@@ -140,7 +141,7 @@ __device__ __forceinline__ void grad_epilogue(Acc<T>& acc, const Quad<T>& qd, do
         r2 = r2 > 0.0 ? r2 : 0.0;  // np.maximum(sq_dist, 0)
 #pragma unroll
         for (int v = 0; v < NV; ++v) rv[v] = vec[2 * v * T + row];
-        const double w = weight(rv, cv, acc.v[mi][0][r]) * exp(-0.5 * r2);
+        const double w = weight(rv, cv, acc.v[mi][0][r]) * cov_dweight<KIND>(r2);
         double wm = (gj < gi && gi < N) ? w : 0.0;
         // (formed here: left to the optimiser, the 32 exponentials sink past the barriers below into the
         // coordinate loop's preheader, and their 32 arguments spill on the way)
@@ -192,6 +193,7 @@ __device__ __forceinline__ void grad_epilogue(Acc<T>& acc, const Quad<T>& qd, do
 // Weight: (alpha_i alpha_j - W_ij) K_ij (grad_epilogue).
 // Tile order: blockIdx.x = I (I + 1) / 2 + J, the deepest tiles first.
 // grid: (nt (nt + 1) / 2, particles)
+template <int KIND = COV_SE>
 __global__ __launch_bounds__(Geo<T>::NTH, 4) void k_lml_grad(int N, int Npad, int nt, int d,
                                                              const double* __restrict__ x,
                                                              const double* __restrict__ ls,
@@ -205,7 +207,7 @@ __global__ __launch_bounds__(Geo<T>::NTH, 4) void k_lml_grad(int N, int Npad, in
   Acc<T> acc;
   w_tile(acc, I, J, Npad, nt, U, smem, qd);
   const double* ap = alpha + (size_t)p * Npad;
-  grad_epilogue<1>(
+  grad_epilogue<1, KIND>(
       acc, qd, smem, I, J, p, N, d, x, ls + (size_t)p * d, [&](int, int g) { return ap[g]; },
       [](const double* ri, const double* cj, double w) { return ri[0] * cj[0] - w; }, partial);
 }

@@ -147,6 +147,7 @@ __global__ __launch_bounds__(NTHR) void k_loo_u(int N, int Npad, const double* _
 // Tile order: all depths are equal, so the tiles below the diagonal go first and the lighter diagonal
 // tiles last (tri_decode_offdiag_first), as k_post_cov.
 // grid: (nt (nt + 1) / 2, particles)
+template <int KIND = COV_SE>
 __global__ __launch_bounds__(Geo<T>::NTH, 4) void k_loo_grad(int N, int Npad, int nt, int d,
                                                              const double* __restrict__ x,
                                                              const double* __restrict__ ls,
@@ -161,7 +162,7 @@ __global__ __launch_bounds__(Geo<T>::NTH, 4) void k_loo_grad(int N, int Npad, in
   Acc<T> acc;
   gram_tile(acc, Bm + (size_t)p * Npad * Npad, Npad, I, J, Npad, smem, qd);
   const double* vp = vec + (size_t)p * LV_N * Npad;
-  grad_epilogue<2>(
+  grad_epilogue<2, KIND>(
       acc, qd, smem, I, J, p, N, d, x, ls + (size_t)p * d,
       [&](int v, int g) { return vp[(size_t)(v == 0 ? LV_ALPHA : LV_U) * Npad + g]; },
       [](const double* ri, const double* cj, double m) { return (ri[1] * cj[0] + cj[1] * ri[0]) - 2.0 * m; }, partial);

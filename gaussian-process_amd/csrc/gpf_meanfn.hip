@@ -444,6 +444,7 @@ __device__ __forceinline__ void proj_tile(Acc<T>& acc, const double* A, const do
 // acc holds the tile of Pt = U^T U - Bt^T Bt; then grad_epilogue on the vector at / a with k_lml_grad's
 // weight.
 // Bt, nBt = -Bt: [particles][mpad][Npad]. grid: (nt (nt + 1) / 2, particles), the deepest tiles first
+template <int KIND = COV_SE>
 __global__ __launch_bounds__(Geo<T>::NTH, 4) void k_mean_grad(int N, int Npad, int nt, int d, int mpad,
                                                               const double* __restrict__ x, const double* __restrict__ ls,
                                                               const double* __restrict__ U, const double* __restrict__ Bt,
@@ -460,7 +461,7 @@ __global__ __launch_bounds__(Geo<T>::NTH, 4) void k_mean_grad(int N, int Npad, i
   const double* bp = Bt + (size_t)p * mpad * Npad;
   proj_tile(acc, Up, bn, bp, Npad, I, J, (nt - I) * T, mpad, smem, qd);
   const double* vp = vec + (size_t)p * Npad;
-  grad_epilogue<1>(
+  grad_epilogue<1, KIND>(
       acc, qd, smem, I, J, p, N, d, x, ls + (size_t)p * d, [&](int, int g) { return vp[g]; },
       [](const double* ri, const double* cj, double w) { return ri[0] * cj[0] - w; }, partial);
 }

@@ -177,6 +177,7 @@ __device__ __forceinline__ void p_syrk(const PItem& a, const PState& st, int J, 
 }
 
 // L tile (J, I) (see the file comment); I = J+1 also reduces and factors diagonal block I.
+template <int KIND = COV_SE>
 __device__ __forceinline__ void p_ltile(const PItem& a, const PState& st, int J, int I, int p, int* sflag, double* lds) {
   const int tid = threadIdx.x, nt = a.nt;
   const size_t ld = (size_t)a.Npad;
@@ -197,7 +198,7 @@ __device__ __forceinline__ void p_ltile(const PItem& a, const PState& st, int J,
   // J have it. The same chunks in the same order: bitwise the one-piece GEMM.
   Acc<T> acc;
   if (J > 1 && p_wait(lc + I, J - 1, lc + J, J - 1, info, st.abort, a.spins, sflag)) return;
-  cov_tile_acc(acc, qd, a.x, a.ls + (size_t)p * a.d, a.d, a.N, J, I, lds);
+  cov_tile_acc<KIND>(acc, qd, a.x, a.ls + (size_t)p * a.d, a.d, a.N, J, I, lds);
   if (J > 0 && !gemm_stream_dl_wait<false, true, TRI_NONE>(acc, Lp + (size_t)J * T * ld, a.Npad, Lp + (size_t)I * T * ld,
                                                            a.Npad, J * T, (J - 1) * T, lds, qd, [&] {
                                                              return p_wait(lc + I, J, lc + J, J, info, st.abort, a.spins,
@@ -311,6 +312,7 @@ __device__ __forceinline__ void p_utile(const PItem& a, const PState& st, int J,
 // what the deadlock-freedom argument needs; and as one item per workgroup the register allocation
 // is k_step's (a loop over items kept the decode and addressing state live across the tile bodies
 // and spilled). The grid equals the number of items, so every workgroup finds a ticket.
+template <int KIND = COV_SE>
 __global__ __launch_bounds__(STEP_NTH, STEP_WAVES_PER_SIMD) void k_factor(PItem a, PState st, int P,
                                                                                 unsigned long long* __restrict__ clk) {
   __shared__ unsigned long long sclk[2];
@@ -361,7 +363,7 @@ __global__ __launch_bounds__(STEP_NTH, STEP_WAVES_PER_SIMD) void k_factor(PItem 
   const int kind = p_decode(tk, P, nt, q, Jc, bc, p, w);
   const int J = Jc;
   if (kind == PK_SYRK) p_syrk(a, st, J, p, &sflag, lds);
-  else if (kind == PK_LTILE) p_ltile(a, st, J, J + 1 + w, p, &sflag, lds);
+  else if (kind == PK_LTILE) p_ltile<KIND>(a, st, J, J + 1 + w, p, &sflag, lds);
   else p_utile(a, st, J, w - (nt - 1 - J), p, &sflag, lds);
   span.stop(clk);
 }

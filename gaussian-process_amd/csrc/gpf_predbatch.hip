@@ -33,23 +33,25 @@ __global__ __launch_bounds__(Geo<T>::NTH, 4) void k_predict_vsq_batch(int Npad, 
 // p's length scales l + p d into out + p ostride, so every element is bitwise what launch_cross_cov
 // gives for that particle (tests/test_predict_batch_gpu.py).
 // grid: (ceil(C/256), ceil(R/CC_R), pc), dynamic LDS cross_cov_lds(d) bytes
-template <int D>
+template <int D, int KIND = COV_SE>
 __global__ __launch_bounds__(NTHR) void k_cross_cov_batch(int N1, int N2, int R, int C, int dd,
                                                           const double* __restrict__ x1, int ld1,
                                                           const double* __restrict__ x2, int ld2,
                                                           const double* __restrict__ l, double* __restrict__ out,
                                                           int64_t ldo, size_t ostride) {
-  cross_cov_block<D>(N1, N2, R, C, dd, x1, ld1, x2, ld2, l + (size_t)blockIdx.z * (D > 0 ? D : dd),
+  cross_cov_block<D, KIND>(N1, N2, R, C, dd, x1, ld1, x2, ld2, l + (size_t)blockIdx.z * (D > 0 ? D : dd),
                      out + (size_t)blockIdx.z * ostride, ldo);
 }
 
-inline void launch_cross_cov_batch(hipStream_t stream, int pc, int N1, int N2, int R, int C, int d, const double* x1,
+inline void launch_cross_cov_batch(hipStream_t stream, int kind, int pc, int N1, int N2, int R, int C, int d, const double* x1,
                                    int ld1, const double* x2, int ld2, const double* l, double* out, int64_t ldo,
                                    size_t ostride) {
   const dim3 grid((unsigned)((C + CC_C - 1) / CC_C), (unsigned)((R + CC_R - 1) / CC_R), (unsigned)pc);
-  with_cross_cov_dim(d, [&](auto D) {
-    hipLaunchKernelGGL(k_cross_cov_batch<D()>, grid, dim3(NTHR), cross_cov_lds(d), stream, N1, N2, R, C, d, x1, ld1, x2, ld2, l,
-                       out, ldo, ostride);
+  with_cov_kind(kind, [&](auto KIND) {
+    with_cross_cov_dim(d, [&](auto D) {
+      hipLaunchKernelGGL((k_cross_cov_batch<D(), KIND()>), grid, dim3(NTHR), cross_cov_lds(d), stream, N1, N2, R, C, d, x1, ld1, x2,
+                         ld2, l, out, ldo, ostride);
+    });
   });
 }
 

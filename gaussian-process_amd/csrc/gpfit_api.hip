@@ -146,6 +146,7 @@ struct gpf_ctx {
   // training data
   int64_t N = 0, Npad = 0;
   int d = 0, nt = 0;
+  int kind = gpf::COV_SE;  // the covariance function (gpf_set_kernel): a model choice, kept across gpf_set_data
   double* d_x = nullptr;
   double* d_y = nullptr;
   double* d_e = nullptr;
@@ -476,9 +477,11 @@ static int run_factor(gpf_ctx* c, int pc, const Knobs& knobs, const double* nfac
     // only the diagonal blocks are built here; k_step computes the other tiles
     const int nbuild = nt > 1 ? 3 * nt : ntri;
     int rc = launch_on(c, st, PC_BUILD, 8.0 * nbuild * BT * BT * (double)gc, [&] {
-      hipLaunchKernelGGL(gpf::k_build_cov, dim3(nbuild, gc), dim3(NTHR), 0, st, N, Np, c->d, c->d_x, c->d_y, c->d_e,
-                         lsg, Lg, yg, ig, (int)(nbuild != ntri), c->d_flag + p0, c->d_cflag + p0,
-                         persist ? c->d_pst : nullptr, (long long)c->cap * nt, nt, nfac ? nfac + p0 : nullptr);
+      gpf::with_cov_kind(c->kind, [&](auto KIND) {
+        hipLaunchKernelGGL(gpf::k_build_cov<KIND()>, dim3(nbuild, gc), dim3(NTHR), 0, st, N, Np, c->d, c->d_x, c->d_y, c->d_e,
+                           lsg, Lg, yg, ig, (int)(nbuild != ntri), c->d_flag + p0, c->d_cflag + p0,
+                           persist ? c->d_pst : nullptr, (long long)c->cap * nt, nt, nfac ? nfac + p0 : nullptr);
+      });
     });
     if (rc) return rc;
     if (ed) continue;  // block 0 is factored by launch 0's diagonal workgroups
@@ -499,8 +502,10 @@ static int run_factor(gpf_ctx* c, int pc, const Knobs& knobs, const double* nfac
     gpf::PState ps_{c->d_pst, c->d_pst + ps, c->d_pst + 2 * ps, reinterpret_cast<unsigned*>(c->d_pst + 3 * ps),
                     c->d_pst + 3 * ps + gpf::PQ_MAX};
     const int rc = launch_on(c, c->stream, PC_PANEL, fl * pc, [&] {
-      hipLaunchKernelGGL(gpf::k_factor, dim3((unsigned)gpf::p_total_items(pc, nt)), dim3(gpf::STEP_NTH), 0, c->stream, a,
-                         ps_, pc, c->prof ? c->d_clk : nullptr);
+      gpf::with_cov_kind(c->kind, [&](auto KIND) {
+        hipLaunchKernelGGL(gpf::k_factor<KIND()>, dim3((unsigned)gpf::p_total_items(pc, nt)), dim3(gpf::STEP_NTH), 0, c->stream,
+                           a, ps_, pc, c->prof ? c->d_clk : nullptr);
+      });
     });
     if (rc) return rc;
     total += fl * pc;
@@ -524,8 +529,11 @@ static int run_factor(gpf_ctx* c, int pc, const Knobs& knobs, const double* nfac
     double* partg = l.split != gpf::SPLIT_NONE ? d_part + l.part_off : nullptr;
     unsigned* cntg = l.split != gpf::SPLIT_NONE ? c->cnt.as<unsigned>() + l.cnt_off : nullptr;
     if (l.split == gpf::SPLIT_ALL && !ed) return bad_arg(c, "internal: all-tile split without the early diagonal factor");
-    const auto kern = l.split == gpf::SPLIT_ALL ? gpf::k_step<gpf::SPLIT_ALL, 1>
-                                                : (ed ? gpf::k_step<gpf::SPLIT_NONE, 1> : gpf::k_step<gpf::SPLIT_NONE, 0>);
+    auto kern = gpf::k_step<gpf::SPLIT_NONE, 0>;
+    gpf::with_cov_kind(c->kind, [&](auto KIND) {
+      kern = l.split == gpf::SPLIT_ALL ? gpf::k_step<gpf::SPLIT_ALL, 1, KIND()>
+                                       : (ed ? gpf::k_step<gpf::SPLIT_NONE, 1, KIND()> : gpf::k_step<gpf::SPLIT_NONE, 0, KIND()>);
+    });
     const int rc = launch_on(c, st, PC_PANEL, fl * gc, [&] {
       hipLaunchKernelGGL(kern, dim3(l.grid), dim3(gpf::STEP_NTH), l.lds, st, l.J, nt, Np, c->d_L + (size_t)p0 * ld * ld,
                          c->d_U + (size_t)p0 * ld * ld, c->d_yb + (size_t)p0 * ld, c->d_s2p + (size_t)p0 * nt * ld,
@@ -751,7 +759,7 @@ static int queue_ks_vsq(gpf_ctx* c, int64_t m, const double* xq, int64_t ldx, do
   const int64_t Np = c->Npad;
   const int nqt = (int)((m + T - 1) / T), Cm = nqt * T;
   int rc = launch(c, PC_PREDK, 8.0 * Np * Cm, [&] {
-    gpf::launch_cross_cov(c->stream, (int)c->N, (int)m, (int)Np, Cm, c->d, c->d_x, (int)c->N, xq, (int)ldx, c->d_ls, ks, ldks);
+    gpf::launch_cross_cov(c->stream, c->kind, (int)c->N, (int)m, (int)Np, Cm, c->d, c->d_x, (int)c->N, xq, (int)ldx, c->d_ls, ks, ldks);
   });
   if (rc) return rc;
   return launch(c, PC_PRED, v_flops(c->nt, Cm), [&] {
@@ -844,6 +852,23 @@ int gpf_set_data(gpf_ctx* c, const double* x, const double* y, const double* e, 
   GPF_HIP(c, hipMemcpy(c->d_y, y, (size_t)N * 8, hipMemcpyHostToDevice));
   GPF_HIP(c, hipMemcpy(c->d_e, e, (size_t)N * 8, hipMemcpyHostToDevice));
   c->h_y.assign(y, y + N);
+  return GPF_OK;
+}
+
+int gpf_set_kernel(gpf_ctx* c, int kind) {
+  if (!c) return GPF_BAD_ARG;
+  if (!gpf::cov_kind_known(kind)) return bad_arg(c, "gpf_set_kernel: unknown kind (0 se, 1 matern32, 2 matern52)");
+  if (kind == c->kind) return GPF_OK;
+  hipSetDevice(c->device);
+  GPF_HIP(c, hipStreamSynchronize(c->stream));
+  clear_graphs(c);  // a replay would launch the other kind's kernels
+  c->kind = kind;
+  return GPF_OK;
+}
+
+int gpf_get_kernel(gpf_ctx* c, int* kind) {
+  if (!c || !kind) return GPF_BAD_ARG;
+  *kind = c->kind;
   return GPF_OK;
 }
 
@@ -1266,9 +1291,9 @@ static int pcov_enqueue(gpf_ctx* c, const Knobs& knobs, const double* ls, const 
   if (rc) return rc;
   // K_s (Np x Cp, zero rows / columns past N / M) and K_ss into Sigma's buffer (zero past M)
   rc = launch(c, PC_PREDK, 8.0 * Np * Cp + 8.0 * Cp * Cp, [&] {
-    gpf::launch_cross_cov(c->stream, (int)c->N, (int)M, (int)Np, (int)Cp, c->d, c->d_x, (int)c->N, xf, (int)Cp, c->d_ls,
+    gpf::launch_cross_cov(c->stream, c->kind, (int)c->N, (int)M, (int)Np, (int)Cp, c->d, c->d_x, (int)c->N, xf, (int)Cp, c->d_ls,
                           ks, Cp);
-    gpf::launch_cross_cov(c->stream, (int)M, (int)M, (int)Cp, (int)Cp, c->d, xf, (int)Cp, xf, (int)Cp, c->d_ls,
+    gpf::launch_cross_cov(c->stream, c->kind, (int)M, (int)M, (int)Cp, (int)Cp, c->d, xf, (int)Cp, xf, (int)Cp, c->d_ls,
                           cov, Cp);
   });
   // V = U K_s, stored, and its per-column partials
@@ -1448,7 +1473,7 @@ static int lin_enqueue(gpf_ctx* c, const Knobs& knobs, void* const* bufs, const 
     const int64_t m = std::min<int64_t>(Cc, M - s);
     const int Cm = (int)(((m + T - 1) / T) * T);
     rc = launch(c, PC_PREDK, 8.0 * (double)Np * Cm, [&] {
-      gpf::launch_cross_cov(st, (int)c->N, (int)m, (int)Np, Cm, d, c->d_x, (int)c->N, xf + s, (int)Mp, c->d_ls, blk, Cc);
+      gpf::launch_cross_cov(st, c->kind, (int)c->N, (int)m, (int)Np, Cm, d, c->d_x, (int)c->N, xf + s, (int)Mp, c->d_ls, blk, Cc);
     });
     if (rc) break;
     const double* ws = wt + (size_t)s * Rp;
@@ -1478,7 +1503,7 @@ static int lin_enqueue(gpf_ctx* c, const Knobs& knobs, void* const* bufs, const 
       const int64_t m2 = std::min<int64_t>(Cc, M - s2);
       const int C2 = (int)(((m2 + T - 1) / T) * T);
       rc = launch(c, PC_PREDK, 8.0 * (double)C1 * C2, [&] {
-        gpf::launch_cross_cov(st, (int)m1, (int)m2, C1, C2, d, xf + s1, (int)Mp, xf + s2, (int)Mp, c->d_ls, blk, Cc);
+        gpf::launch_cross_cov(st, c->kind, (int)m1, (int)m2, C1, C2, d, xf + s1, (int)Mp, xf + s2, (int)Mp, c->d_ls, blk, Cc);
         if (s1 == s2)
           hipLaunchKernelGGL(gpf::k_lin_unit_diag, dim3((unsigned)((m1 + NTHR - 1) / NTHR)), dim3(NTHR), 0, st, (int)m1, blk, Cc);
       });
@@ -2033,7 +2058,7 @@ int gpf_kernel(gpf_ctx* c, const double* x1, int64_t N1, const double* x2, int64
   GPF_HIP(c, hipMemcpyAsync(dx2, x2, (size_t)N2 * d * 8, hipMemcpyHostToDevice, c->stream));
   GPF_HIP(c, hipMemcpyAsync(dl, l, (size_t)d * 8, hipMemcpyHostToDevice, c->stream));
   int rc = launch(c, PC_BUILD, 8.0 * N1 * N2, [&] {
-    gpf::launch_cross_cov(c->stream, (int)N1, (int)N2, (int)N1, (int)N2, d, dx1, (int)N1, dx2, (int)N2, dl, dout, (int64_t)N2);
+    gpf::launch_cross_cov(c->stream, c->kind, (int)N1, (int)N2, (int)N1, (int)N2, d, dx1, (int)N1, dx2, (int)N2, dl, dout, (int64_t)N2);
   });
   if (rc == GPF_OK) {
     if (hipMemcpyAsync(out, dout, (size_t)N1 * N2 * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
@@ -2190,8 +2215,10 @@ int gpf_lml_batch(gpf_ctx* c, const double* ls, int P, double* lml, double* grad
     });
   };
   o.tiles = [&](int pc, double* partial) {
-    hipLaunchKernelGGL(gpf::k_lml_grad, dim3((unsigned)(nt * (nt + 1) / 2), pc), dim3(gpf::Geo<T>::NTH), 0, c->stream, (int)N,
-                       (int)Np, nt, d, c->d_x, c->d_ls, c->d_U, c->d_mu, partial);
+    gpf::with_cov_kind(c->kind, [&](auto KIND) {
+      hipLaunchKernelGGL(gpf::k_lml_grad<KIND()>, dim3((unsigned)(nt * (nt + 1) / 2), pc), dim3(gpf::Geo<T>::NTH), 0, c->stream,
+                         (int)N, (int)Np, nt, d, c->d_x, c->d_ls, c->d_U, c->d_mu, partial);
+    });
   };
   o.fetch = [&](int, int pc) -> int {
     GPF_HIP(c, hipMemcpyAsync(c->h_loss, c->d_loss, (size_t)pc * 8, hipMemcpyDeviceToHost, c->stream));
@@ -2262,8 +2289,10 @@ int gpf_loo_batch(gpf_ctx* c, const double* ls, int P, double* lpd, double* grad
     });
   };
   o.tiles = [&](int pc, double* partial) {
-    hipLaunchKernelGGL(gpf::k_loo_grad, dim3((unsigned)ntile, pc), dim3(gpf::Geo<T>::NTH), 0, c->stream, (int)N, (int)Np, nt, d,
-                       c->d_x, c->d_ls, d_B, d_vec, partial);
+    gpf::with_cov_kind(c->kind, [&](auto KIND) {
+      hipLaunchKernelGGL(gpf::k_loo_grad<KIND()>, dim3((unsigned)ntile, pc), dim3(gpf::Geo<T>::NTH), 0, c->stream, (int)N, (int)Np,
+                         nt, d, c->d_x, c->d_ls, d_B, d_vec, partial);
+    });
   };
   o.fetch = [&](int s, int pc) -> int {
     if (mu)
@@ -2341,8 +2370,10 @@ int gpf_lml_hyper_batch(gpf_ctx* c, const double* th, int P, double* lml, double
   o.tiles = [&](int pc, double* partial) {
     hipLaunchKernelGGL(gpf::k_hyper_scale, dim3((unsigned)((N + NTHR - 1) / NTHR), pc), dim3(NTHR), 0, c->stream, (int)N,
                        (int)Np, d_al, d_as, d_sc);
-    hipLaunchKernelGGL(gpf::k_lml_grad, dim3((unsigned)(nt * (nt + 1) / 2), pc), dim3(gpf::Geo<T>::NTH), 0, c->stream, (int)N,
-                       (int)Np, nt, d, c->d_x, c->d_ls, c->d_U, d_sc, partial);
+    gpf::with_cov_kind(c->kind, [&](auto KIND) {
+      hipLaunchKernelGGL(gpf::k_lml_grad<KIND()>, dim3((unsigned)(nt * (nt + 1) / 2), pc), dim3(gpf::Geo<T>::NTH), 0, c->stream,
+                         (int)N, (int)Np, nt, d, c->d_x, c->d_ls, c->d_U, d_sc, partial);
+    });
   };
   o.fetch = [&](int, int pc) -> int {
     GPF_HIP(c, hipMemcpyAsync(ho.data(), d_out, (size_t)pc * gpf::HV_N * 8, hipMemcpyDeviceToHost, c->stream));
@@ -2505,8 +2536,10 @@ int gpf_lml_mean_batch(gpf_ctx* c, const double* th, int P, double* lml, double*
     });
   };
   o.tiles = [&](int pc, double* partial) {
-    hipLaunchKernelGGL(gpf::k_mean_grad, dim3((unsigned)ntile, pc), dim3(gpf::Geo<T>::NTH), 0, c->stream, (int)N, (int)Np, nt, d,
-                       mp, c->d_x, c->d_ls, c->d_U, b.Bt, b.nBt, b.sc, partial);
+    gpf::with_cov_kind(c->kind, [&](auto KIND) {
+      hipLaunchKernelGGL(gpf::k_mean_grad<KIND()>, dim3((unsigned)ntile, pc), dim3(gpf::Geo<T>::NTH), 0, c->stream, (int)N, (int)Np,
+                         nt, d, mp, c->d_x, c->d_ls, c->d_U, b.Bt, b.nBt, b.sc, partial);
+    });
   };
   o.fetch = [&](int, int pc) -> int {
     GPF_HIP(c, hipMemcpyAsync(ho.data(), b.out, (size_t)pc * gpf::MV_N * 8, hipMemcpyDeviceToHost, c->stream));
@@ -2820,12 +2853,12 @@ int gpf_predict_batch(gpf_ctx* c, const double* ls, int P, const double* w, cons
       // the one launch 0.13; profiles/predict_batch/bench.json)
       rc = launch(c, PC_PREDK, 8.0 * Np * Cm * (double)pc, [&] {
         if (ks_batched) {
-          gpf::launch_cross_cov_batch(c->stream, pc, (int)N, (int)m, (int)Np, Cm, d, c->d_x, (int)N, d_xf + s0, (int)Mp,
+          gpf::launch_cross_cov_batch(c->stream, c->kind, pc, (int)N, (int)m, (int)Np, Cm, d, c->d_x, (int)N, d_xf + s0, (int)Mp,
                                       c->d_ls, d_ks, Cq, (size_t)Np * Cq);
           return;
         }
         for (int q = 0; q < pc; ++q)
-          gpf::launch_cross_cov(c->stream, (int)N, (int)m, (int)Np, Cm, d, c->d_x, (int)N, d_xf + s0, (int)Mp,
+          gpf::launch_cross_cov(c->stream, c->kind, (int)N, (int)m, (int)Np, Cm, d, c->d_x, (int)N, d_xf + s0, (int)Mp,
                                 c->d_ls + (size_t)q * d, d_ks + (size_t)q * Np * Cq, Cq);
       });
       if (rc) break;

@@ -13,6 +13,8 @@ from pathlib import Path
 
 import numpy as np
 
+from .kernels import KINDS, kernel_kind
+
 PKG_DIR = Path(__file__).resolve().parent.parent
 LIB_PATH = Path(os.environ.get("GPFIT_LIB", PKG_DIR / "libgpfit.so"))
 
@@ -35,6 +37,8 @@ SIGNATURES = {
     "gpf_last_error": (ctypes.c_char_p, [_vp]),
     "gpf_set_data": (ctypes.c_int, [_vp, _dp, _dp, _dp, ctypes.c_int64, ctypes.c_int]),
     "gpf_set_grid": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int, _dp, _dp]),
+    "gpf_set_kernel": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "gpf_get_kernel": (ctypes.c_int, [_vp, _ip]),
     "gpf_eval_batch": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _dp, _dp, _dp, _ip]),
     "gpf_predict": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int64, ctypes.c_int64, _dp, _dp]),
     "gpf_predict_cov": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int64, _dp, _dp]),
@@ -200,6 +204,18 @@ def default_device():
     return int(os.environ.get("GPFIT_DEVICE", os.environ.get("LOCAL_RANK", "0")))
 
 
+def use_kernel(ctx, kernel):
+    """Set ``kernel`` on the context a call is about to use: every entry point with a kernel= keyword
+    does this on every call, so a call without the keyword is "se" whatever ran before on a shared
+    context. A stand-in context without set_kernel (the host tests') can only be "se"."""
+    kind = kernel_kind(kernel)
+    setter = getattr(ctx, "set_kernel", None)
+    if setter is not None:
+        setter(kernel)
+    elif kind != 0:
+        raise ValueError(f"kernel={kernel!r}: this context has no set_kernel")
+
+
 class Context:
     """One HIP device, one stream, device-resident training data (gpf_ctx)."""
 
@@ -256,6 +272,23 @@ class Context:
         self._data_key = key
         self._grid_key = None
         self.m = 0  # gpf_set_data discards the mean function's basis
+
+    def set_kernel(self, kernel):
+        """The covariance kernel of every later call on this context: "se" (the default, the
+        reference's kernel_func), "matern32" or "matern52" (gpf_set_kernel; gpfit.kernels has the
+        formulas). Needs no data and persists across set_data. An unknown name is a ValueError before
+        the library is called. On the process-wide default_context() the kind does not outlive the next
+        drop-in call: GP(), kernel_func(), evaluate_loss() and every entry point with a kernel= keyword set
+        their own (the keyword's, "se" without it) on the context they use."""
+        kind = kernel_kind(kernel)
+        self._check(self.lib.gpf_set_kernel(self._h, kind), "gpf_set_kernel")
+
+    @property
+    def kernel_name(self):
+        """The context's covariance kernel (gpf_get_kernel): "se", "matern32" or "matern52"."""
+        kind = ctypes.c_int(-1)
+        self._check(self.lib.gpf_get_kernel(self._h, ctypes.byref(kind)), "gpf_get_kernel")
+        return KINDS[kind.value]
 
     def set_grid(self, sigma_vals, expected, lo, hi):
         s, ex = _f64(sigma_vals), _f64(expected)

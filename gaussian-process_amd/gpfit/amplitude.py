@@ -27,7 +27,8 @@ import inspect
 
 import numpy as np
 
-from ._lib import default_comm, default_context
+from ._lib import default_comm, default_context, use_kernel
+from .kernels import kernel_kind
 from .mle import LOWER_FRACTION, NUM_POLISH, NUM_STARTS, _call, polish_log
 from .swarm import MAX_POINTS, centred_lhs, prepare, share_seed
 
@@ -47,9 +48,11 @@ def scaled_data(y, e, a, s):
     return y / a, e * (s / a)
 
 
-def predict_hyper(x, y, e, x_fit, theta, ctx=None):
+def predict_hyper(x, y, e, x_fit, theta, ctx=None, kernel="se"):
     """GP mean and sd at x_fit (d, M) under theta = (l_1 .. l_d, a, s): (mu (M,), sd (M,)), a times
-    the unit model's prediction on ``scaled_data`` (sd: of the latent f, clipped as GP's)."""
+    the unit model's prediction on ``scaled_data`` (sd: of the latent f, clipped as GP's).
+    ``kernel``: the covariance kernel, "se" (default), "matern32" or "matern52" (gpfit.kernels), set on the context on every call."""
+    kernel_kind(kernel)
     x = np.asarray(x, dtype=np.float64)
     theta = np.asarray(theta, dtype=np.float64).reshape(-1)
     if theta.shape[0] != x.shape[0] + 2:
@@ -59,6 +62,7 @@ def predict_hyper(x, y, e, x_fit, theta, ctx=None):
     if ctx is None:
         ctx = default_context()
     ctx.set_data(x, ys, es)
+    use_kernel(ctx, kernel)
     mu, sd = ctx.predict(theta[:-2], np.asarray(x_fit, dtype=np.float64))
     return mu * a, sd * a
 
@@ -87,13 +91,14 @@ def _value_and_q(value_and_grad, theta, n, counts):
 
 
 def _fit_theta(x, y, e, *, who, lost, pin, setup, done_msg, num_starts, num_polish, max_points, seed, value_and_grad,
-               ctx, verbose):
+               ctx, verbose, kernel="se"):
     """The two-stage driver behind fit_hyper and gpfit.meanfn.fit_mean. ``lost``: the degrees of freedom
     a marginalised mean takes (m; 0 for fit_hyper), so the best amplitude of a start is
     sqrt(Q / (N - lost)). ``setup(ctx or None, x, y, e)`` (optional) is called with the prepared points
     once the data are on the device and returns the evaluator (fit_mean sets its basis there); without
     it the evaluator is the injected one or gpf_lml_hyper_batch. ``pin``: a = s = 1, only the length
     scales are fitted (the starts in the length-scale box, stage 2 in log l)."""
+    kernel_kind(kernel)
     x = np.asarray(x, dtype=np.float64)
     y = np.asarray(y, dtype=np.float64)
     e = np.asarray(e, dtype=np.float64)
@@ -114,6 +119,7 @@ def _fit_theta(x, y, e, *, who, lost, pin, setup, done_msg, num_starts, num_poli
             value_and_grad = setup(None, x, y, e)
     else:
         ctx.set_data(x, y, e)
+        use_kernel(ctx, kernel)
         value_and_grad = setup(ctx, x, y, e) if setup is not None else _device_evaluator(ctx)
         comm = default_comm(ctx)
     seed = share_seed(seed, comm)
@@ -179,7 +185,7 @@ def _fit_result(polished, counts, lower, upper, starts, start_lml, d, done_msg, 
 
 
 def fit_hyper(x, y, e, *, num_starts=NUM_STARTS, num_polish=NUM_POLISH, max_points=MAX_POINTS, seed=None,
-              value_and_grad=None, ctx=None, verbose=True):
+              value_and_grad=None, ctx=None, verbose=True, kernel="se"):
     """theta = (l_1 .. l_d, a, s) that maximises the log marginal likelihood: (theta (d + 2,), info).
 
     fit_lml's signature and semantics. ``value_and_grad(theta (P, d + 2)) -> (lml (P,), grad (P, d + 2))``
@@ -194,9 +200,9 @@ def fit_hyper(x, y, e, *, num_starts=NUM_STARTS, num_polish=NUM_POLISH, max_poin
 
     info: "lml" (at theta), "evals", "grad_evals", "box" (lower, upper: d + 2 each), "starts"
     (theta (num_starts, d + 2), lml) and "polished" (one dict per polished start: start, x, lml,
-    start_lml, nfev, nit, message).
+    start_lml, nfev, nit, message). ``kernel`` as fit_lml's.
     """
     return _fit_theta(x, y, e, who="fit_hyper", lost=0, pin=False, setup=None,
                       done_msg="Marginal-likelihood fit of length scales, amplitude and noise scale completed.",
                       num_starts=num_starts, num_polish=num_polish, max_points=max_points, seed=seed,
-                      value_and_grad=value_and_grad, ctx=ctx, verbose=verbose)
+                      value_and_grad=value_and_grad, ctx=ctx, verbose=verbose, kernel=kernel)

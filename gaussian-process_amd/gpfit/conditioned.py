@@ -20,7 +20,8 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._lib import default_context
+from ._lib import default_context, use_kernel
+from .kernels import kernel_kind
 from .linear import check_weights
 
 METHODS = ("stream", "dense")
@@ -61,7 +62,7 @@ def conditioned_from(mu, cov, weights, values, noise):
 
 
 def predict_conditioned(x_known, y_known, e_known, x_fit, lengths, weights, values, noise, method="stream", chunk=0,
-                        ctx=None):
+                        ctx=None, kernel="se"):
     """The latent GP at x_fit (d, M) conditioned on the training data and on the measured functionals:
     (mu' (M,), sd' (M,), info), sd' = sqrt(clip(var', 1e-12)) as GP()'s. info: "chi2", "fmean", "fcov"
     (the functionals before conditioning) and "method".
@@ -69,7 +70,8 @@ def predict_conditioned(x_known, y_known, e_known, x_fit, lengths, weights, valu
     method="stream" (the default): gpf_predict_conditioned on this process's GPU, ``chunk`` query
     points per pass (0: the library's default). method="dense": predict_cov's (mu, Sigma) copied back,
     then conditioned_from. With R = 0 the plain prediction. ``ctx``: the context to use (default: this
-    process's)."""
+    process's). ``kernel``: the covariance kernel, "se" (default), "matern32" or "matern52" (gpfit.kernels), set on the context on every call."""
+    kernel_kind(kernel)
     if method not in METHODS:
         raise ValueError(f"method must be one of {METHODS}, not {method!r}")
     x_known = np.asarray(x_known, dtype=np.float64)
@@ -84,6 +86,7 @@ def predict_conditioned(x_known, y_known, e_known, x_fit, lengths, weights, valu
     if ctx is None:
         ctx = default_context()
     ctx.set_data(x_known, y_known, e_known)
+    use_kernel(ctx, kernel)
     if method == "dense":
         mu, cov, info = conditioned_from(*ctx.predict_cov(lengths, x_fit), w, b, s)
         return mu, np.sqrt(np.maximum(np.diag(cov), 1e-12)), dict(info, method=method)

@@ -23,7 +23,8 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._lib import default_comm, default_context
+from ._lib import default_comm, default_context, use_kernel
+from .kernels import kernel_kind
 from .mle import LOWER_FRACTION, _call, _device_evaluator, fit_lml
 from .swarm import MAX_POINTS, prepare, share_seed
 
@@ -65,7 +66,7 @@ def mixture_from(mu_PM, sd_PM, weights=None):
 
 
 def sample_hyper(x, y, e, best_l=None, n_samples=32, inflate=1.5, seed=None, max_points=MAX_POINTS,
-                 value_and_grad=None, ctx=None, verbose=False):
+                 value_and_grad=None, ctx=None, verbose=False, kernel="se"):
     """K = n_samples length-scale samples and their weights: (ls (K, d), weights (K,), info).
 
     The data preparation and the box are fit_lml's; best_l=None runs fit_lml first. In t = log l the
@@ -82,7 +83,8 @@ def sample_hyper(x, y, e, best_l=None, n_samples=32, inflate=1.5, seed=None, max
     ``value_and_grad(positions (P, d)) -> (lml (P,), grad (P, d))``, the gradient in l, injects an
     evaluator exactly as in fit_lml; the default is gpf_lml_batch on this process's GPU.
     info: "ess" (= 1 / sum w^2), "hessian", "cov" (the proposal's), "lml" (K,), "best_l", "evals"
-    (value evaluations, fit_lml's included) and "box"."""
+    (value evaluations, fit_lml's included) and "box". ``kernel`` as fit_lml's."""
+    kernel_kind(kernel)
     x = np.asarray(x, dtype=np.float64)
     y = np.asarray(y, dtype=np.float64)
     e = np.asarray(e, dtype=np.float64)
@@ -97,7 +99,7 @@ def sample_hyper(x, y, e, best_l=None, n_samples=32, inflate=1.5, seed=None, max
     evals = 0
     if best_l is None:
         best_l, fit = fit_lml(x, y, e, max_points=max_points, seed=seed, value_and_grad=value_and_grad, ctx=ctx,
-                              verbose=verbose)
+                              verbose=verbose, kernel=kernel)
         evals += fit["evals"]
     xs, ys, es, lower, upper, _, _ = prepare(x, y, e, max_points=max_points, verbose=verbose,
                                              ctx=None if injected else ctx)
@@ -112,6 +114,7 @@ def sample_hyper(x, y, e, best_l=None, n_samples=32, inflate=1.5, seed=None, max
         comm = default_comm()
     else:
         ctx.set_data(xs, ys, es)
+        use_kernel(ctx, kernel)
         value_and_grad = _device_evaluator(ctx)
         comm = default_comm(ctx)
     seed = share_seed(seed, comm)
@@ -163,7 +166,8 @@ def sample_hyper(x, y, e, best_l=None, n_samples=32, inflate=1.5, seed=None, max
     return ls, w, info
 
 
-def predict_marginal(x, y, e, x_fit, ls=None, weights=None, method="batch", chunk=0, ctx=None, **sample_kwargs):
+def predict_marginal(x, y, e, x_fit, ls=None, weights=None, method="batch", chunk=0, ctx=None, kernel="se",
+                     **sample_kwargs):
     """The prediction at x_fit (d, M) marginalised over the length scales: (mix_mu (M,), mix_sd (M,),
     info). ``ls`` (K, d) with ``weights`` (K,) (None: equal) are the samples; ls=None draws them with
     sample_hyper(x, y, e, **sample_kwargs). The prediction itself uses all of (x, y, e), as GP() does.
@@ -171,7 +175,9 @@ def predict_marginal(x, y, e, x_fit, ls=None, weights=None, method="batch", chun
     method="batch": one gpf_predict_batch call on this process's GPU, ``chunk`` query points per pass
     (0: the library's default). method="loop": K predict() calls and mixture_from, the yardstick.
     info: "ls", "weights" (normalised), "method", "ess" and, when the samples were drawn here,
-    sample_hyper's info under "sample"."""
+    sample_hyper's info under "sample". ``kernel``: the covariance kernel of the sampling and of the
+    prediction ("se", "matern32" or "matern52"; gpfit.kernels), set on the context on every call."""
+    kernel_kind(kernel)
     if method not in METHODS:
         raise ValueError(f"method must be one of {METHODS}, not {method!r}")
     x = np.asarray(x, dtype=np.float64)
@@ -186,7 +192,7 @@ def predict_marginal(x, y, e, x_fit, ls=None, weights=None, method="batch", chun
             raise ValueError("weights need their ls")
         if ctx is None and sample_kwargs.get("value_and_grad") is None:
             ctx = default_context()
-        ls, weights, sample = sample_hyper(x, y, e, ctx=ctx, **sample_kwargs)
+        ls, weights, sample = sample_hyper(x, y, e, ctx=ctx, kernel=kernel, **sample_kwargs)
         info["sample"] = sample
     elif sample_kwargs:
         raise ValueError(f"with ls given, sample_hyper's arguments {sorted(sample_kwargs)} are not used")
@@ -202,6 +208,7 @@ def predict_marginal(x, y, e, x_fit, ls=None, weights=None, method="batch", chun
     if ctx is None:
         ctx = default_context()
     ctx.set_data(x, y, e)
+    use_kernel(ctx, kernel)
     if method == "batch":
         mix_mu, mix_sd, _ = ctx.predict_batch(ls, x_fit, weights=w, chunk=int(chunk))
         return mix_mu, mix_sd, info

@@ -17,7 +17,8 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._lib import default_context
+from ._lib import default_context, use_kernel
+from .kernels import kernel_kind
 
 METHODS = ("stream", "dense")
 KINDS = ("mean", "sum")
@@ -68,14 +69,16 @@ def region_weights(x_fit, regions, kind="mean"):
     return w
 
 
-def predict_linear(x_known, y_known, e_known, x_fit, lengths, weights, method="stream", chunk=0, ctx=None):
+def predict_linear(x_known, y_known, e_known, x_fit, lengths, weights, method="stream", chunk=0, ctx=None, kernel="se"):
     """The functionals A f of the latent GP f at x_fit (d, M), A = weights (R, M):
     (mean (R,), cov (R, R), info) with mean = A mu and cov = A Sigma A^T.
 
     method="stream" (the default): gpf_predict_linear on this process's GPU, ``chunk`` query points per
     pass (0: the library's default); info also carries "prior" = A K_ss A^T, the functionals' prior
     covariance. method="dense": predict_cov's (mu, Sigma) copied back, then functionals_from.
-    info["method"] reports the method. ``ctx``: the context to use (default: this process's)."""
+    info["method"] reports the method. ``ctx``: the context to use (default: this process's).
+    ``kernel``: the covariance kernel, "se" (default), "matern32" or "matern52" (gpfit.kernels), set on the context on every call."""
+    kernel_kind(kernel)
     if method not in METHODS:
         raise ValueError(f"method must be one of {METHODS}, not {method!r}")
     x_known = np.asarray(x_known, dtype=np.float64)
@@ -89,6 +92,7 @@ def predict_linear(x_known, y_known, e_known, x_fit, lengths, weights, method="s
     if ctx is None:
         ctx = default_context()
     ctx.set_data(x_known, y_known, e_known)
+    use_kernel(ctx, kernel)
     if method == "dense":
         mean, cov = functionals_from(*ctx.predict_cov(lengths, x_fit), w)
         return mean, cov, {"method": method}

@@ -19,22 +19,26 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._lib import default_context
+from ._lib import default_context, use_kernel
+from .kernels import kernel_kind
 from .mle import NUM_POLISH, NUM_STARTS, fit_gradient
 from .swarm import MAX_POINTS
 
 
-def loo_predict(x, y, e, lengths, ctx=None):
+def loo_predict(x, y, e, lengths, ctx=None, kernel="se"):
     """Every training point predicted from the others at the length scales ``lengths`` (d,):
     (mu (N,), sd (N,), info). info: "lpd" (the LOO log predictive density), "pulls"
     ((y - mu) / sd) and "coverage" (the fractions of |pull| <= 1 and <= 2: 0.683 and 0.954 for
-    honest error bars). LinAlgError if the covariance is not positive definite."""
+    honest error bars). LinAlgError if the covariance is not positive definite.
+    ``kernel``: the covariance kernel, "se" (default), "matern32" or "matern52" (gpfit.kernels), set on the context on every call."""
+    kernel_kind(kernel)
     x = np.asarray(x, dtype=np.float64)
     y = np.asarray(y, dtype=np.float64)
     e = np.asarray(e, dtype=np.float64)
     if ctx is None:
         ctx = default_context()
     ctx.set_data(x, y, e)
+    use_kernel(ctx, kernel)
     lpd, _, mu, sd = ctx.loo_batch(np.asarray(lengths, dtype=np.float64).reshape(1, -1), grad=False, points=True)
     mu, sd = mu[0], sd[0]
     pulls = (y.reshape(-1) - mu) / sd
@@ -50,7 +54,7 @@ def _device_evaluator(ctx):
 
 
 def fit_loo(x, y, e, *, num_starts=NUM_STARTS, num_polish=NUM_POLISH, max_points=MAX_POINTS, seed=None,
-            value_and_grad=None, ctx=None, verbose=True):
+            value_and_grad=None, ctx=None, verbose=True, kernel="se"):
     """Length scales that maximise the LOO log predictive density: (best_l (d,), info).
 
     fit_lml's signature and semantics with lpd in place of the log marginal likelihood:
@@ -58,9 +62,9 @@ def fit_loo(x, y, e, *, num_starts=NUM_STARTS, num_polish=NUM_POLISH, max_points
     tests); the default is gpf_loo_batch on this process's GPU. A point whose covariance is not
     positive definite is a losing point, never an error. info: "lpd" (at best_l), "evals",
     "grad_evals", "box", "starts" (positions, lpd) and "polished" (one dict per polished start:
-    start, x, lpd, start_lpd, nfev, nit, message).
+    start, x, lpd, start_lpd, nfev, nit, message). ``kernel`` as fit_lml's.
     """
     return fit_gradient(x, y, e, who="fit_loo", key="lpd", done_msg="Leave-one-out fit completed.",
                         value_label="LOO log predictive density:", device_evaluator=_device_evaluator,
                         num_starts=num_starts, num_polish=num_polish, max_points=max_points, seed=seed,
-                        value_and_grad=value_and_grad, ctx=ctx, verbose=verbose)
+                        value_and_grad=value_and_grad, ctx=ctx, verbose=verbose, kernel=kernel)

@@ -35,8 +35,9 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._lib import MEAN_MAX, default_context
+from ._lib import MEAN_MAX, default_context, use_kernel
 from .amplitude import _fit_theta, scaled_data
+from .kernels import kernel_kind
 from .mle import NUM_POLISH, NUM_STARTS
 from .swarm import MAX_POINTS
 
@@ -187,10 +188,12 @@ def predict_mean_closed_form(x, y, e, H, theta, x_fit, h_fit):
     return mu, np.sqrt(var), beta, Ainv
 
 
-def predict_mean(x, y, e, x_fit, theta, kind="constant", ctx=None, want_beta=False):
+def predict_mean(x, y, e, x_fit, theta, kind="constant", ctx=None, want_beta=False, kernel="se"):
     """GP mean and sd at x_fit (d, M) under theta = (l_1 .. l_d, a, s) with the marginalised polynomial
     mean ``kind``: (mu (M,), sd (M,)), a times the unit model's gpf_predict_mean on ``scaled_data``; with
-    want_beta also (beta (m,), cov(beta) (m, m)) in the data's units."""
+    want_beta also (beta (m,), cov(beta) (m, m)) in the data's units.
+    ``kernel``: the covariance kernel, "se" (default), "matern32" or "matern52" (gpfit.kernels), set on the context on every call."""
+    kernel_kind(kernel)
     x = np.asarray(x, dtype=np.float64)
     theta = np.asarray(theta, dtype=np.float64).reshape(-1)
     if x.ndim != 2 or theta.shape[0] != x.shape[0] + 2:
@@ -205,6 +208,7 @@ def predict_mean(x, y, e, x_fit, theta, kind="constant", ctx=None, want_beta=Fal
     if ctx is None:
         ctx = default_context()
     ctx.set_data(x, ys, es)
+    use_kernel(ctx, kernel)
     ctx.set_basis(H)
     out = ctx.predict_mean(theta[:-2], x_fit, h_fit, want_beta=want_beta)
     if want_beta:
@@ -213,7 +217,7 @@ def predict_mean(x, y, e, x_fit, theta, kind="constant", ctx=None, want_beta=Fal
 
 
 def fit_mean(x, y, e, *, kind="constant", full=True, num_starts=NUM_STARTS, num_polish=NUM_POLISH,
-             max_points=MAX_POINTS, seed=None, value_and_grad=None, ctx=None, verbose=True):
+             max_points=MAX_POINTS, seed=None, value_and_grad=None, ctx=None, verbose=True, kernel="se"):
     """theta = (l_1 .. l_d, a, s) that maximises the restricted log marginal likelihood under the
     marginalised polynomial mean ``kind``: (theta (d + 2,), info). gpfit.amplitude.fit_hyper's
     signature, stages and info (the same driver), with the best amplitude of a start a = sqrt(Q' / (N - m)),
@@ -221,7 +225,7 @@ def fit_mean(x, y, e, *, kind="constant", full=True, num_starts=NUM_STARTS, num_
     (subsampled) points the fit ran on. ``full=False`` pins a = s = 1 and fits the length scales only.
     ``value_and_grad(theta (P, d + 2)) -> (lml (P,), grad (P, d + 2))`` injects an evaluator (the CPU
     tests; it is handed the prepared points as ``value_and_grad.bind(x, y, e, H)`` if it has that
-    attribute); the default is gpf_lml_mean_batch on this process's GPU."""
+    attribute); the default is gpf_lml_mean_batch on this process's GPU. ``kernel`` as fit_lml's."""
     x = np.asarray(x, dtype=np.float64)
     if x.ndim != 2:
         raise ValueError("x must be (d, N)")
@@ -247,7 +251,7 @@ def fit_mean(x, y, e, *, kind="constant", full=True, num_starts=NUM_STARTS, num_
     best, info = _fit_theta(x, y, e, who="fit_mean", lost=m, pin=not full, setup=setup,
                             done_msg="Restricted-likelihood fit of length scales, amplitude and noise scale completed.",
                             num_starts=num_starts, num_polish=num_polish, max_points=max_points, seed=seed,
-                            value_and_grad=value_and_grad, ctx=ctx, verbose=verbose)
+                            value_and_grad=value_and_grad, ctx=ctx, verbose=verbose, kernel=kernel)
     if value_and_grad is None:  # (the fit left its data and basis on the context)
         info["beta"] = (ctx or default_context()).lml_mean_batch(best[None, :], grad=False, strict=False,
                                                                  want_beta=True)[2][0]

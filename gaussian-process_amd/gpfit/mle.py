@@ -23,7 +23,8 @@ import inspect
 
 import numpy as np
 
-from ._lib import default_comm, default_context
+from ._lib import default_comm, default_context, use_kernel
+from .kernels import kernel_kind
 from .swarm import MAX_POINTS, centred_lhs, prepare, share_seed
 
 NUM_STARTS = 40
@@ -90,10 +91,11 @@ def polish_log(value_and_grad, starts, start_val, order, lower, upper, key, coun
 
 
 def fit_gradient(x, y, e, *, who, key, done_msg, value_label, device_evaluator, num_starts, num_polish, max_points,
-                 seed, value_and_grad, ctx, verbose):
+                 seed, value_and_grad, ctx, verbose, kernel="se"):
     """The two-stage driver behind fit_lml and gpfit.loo.fit_loo: maximises the value an evaluator
     returns with its gradient in the length scales. ``who`` names the caller in messages, ``key`` the
     value in info ("lml", "lpd"), ``device_evaluator(ctx)`` builds the default evaluator."""
+    kernel_kind(kernel)
     x = np.asarray(x, dtype=np.float64)
     y = np.asarray(y, dtype=np.float64)
     e = np.asarray(e, dtype=np.float64)
@@ -109,6 +111,7 @@ def fit_gradient(x, y, e, *, who, key, done_msg, value_label, device_evaluator, 
         comm = default_comm()
     else:
         ctx.set_data(x, y, e)
+        use_kernel(ctx, kernel)
         value_and_grad = device_evaluator(ctx)
         comm = default_comm(ctx)
     seed = share_seed(seed, comm)
@@ -136,7 +139,7 @@ def fit_gradient(x, y, e, *, who, key, done_msg, value_label, device_evaluator, 
 
 
 def fit_lml(x, y, e, *, num_starts=NUM_STARTS, num_polish=NUM_POLISH, max_points=MAX_POINTS, seed=None,
-            value_and_grad=None, ctx=None, verbose=True):
+            value_and_grad=None, ctx=None, verbose=True, kernel="se"):
     """Length scales that maximise the log marginal likelihood: (best_l (d,), info).
 
     ``value_and_grad(positions (P, d)) -> (lml (P,), grad (P, d))`` injects an evaluator (the CPU
@@ -145,8 +148,10 @@ def fit_lml(x, y, e, *, num_starts=NUM_STARTS, num_polish=NUM_POLISH, max_points
     every rank runs the same seeded fit redundantly. info: "lml" (at best_l), "evals" (value
     evaluations), "grad_evals", "box" (lower, upper), "starts" (positions, lml) and "polished" (one
     dict per polished start: start, x, lml, start_lml, nfev, nit, message).
+    ``kernel``: the covariance kernel, "se" (default), "matern32" or "matern52" (gpfit.kernels), set on the context on every call. An injected
+    evaluator brings its own.
     """
     return fit_gradient(x, y, e, who="fit_lml", key="lml", done_msg="Marginal-likelihood fit completed.",
                         value_label="Log marginal likelihood:", device_evaluator=_device_evaluator,
                         num_starts=num_starts, num_polish=num_polish, max_points=max_points, seed=seed,
-                        value_and_grad=value_and_grad, ctx=ctx, verbose=verbose)
+                        value_and_grad=value_and_grad, ctx=ctx, verbose=verbose, kernel=kernel)

@@ -26,7 +26,8 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._lib import JITTERS, check_jitters, default_context   # JITTERS: from GP_func.py:39's variance floor, x 100 per failure
+from ._lib import JITTERS, check_jitters, default_context, use_kernel   # JITTERS: from GP_func.py:39's variance floor, x 100 per failure
+from .kernels import kernel_kind
 
 METHODS = ("host", "device")
 
@@ -61,7 +62,7 @@ def draws_from(mu, cov, n_draws=1, seed=None, z=None):
 
 
 def sample_posterior(x_known, y_known, e_known, x_fit, lengths, n_draws, seed=None, ctx=None, mean_and_cov=None,
-                     method="host", jitters=JITTERS):
+                     method="host", jitters=JITTERS, kernel="se"):
     """n_draws joint draws of the latent GP at x_fit (d, M): (draws (n_draws, M), info).
 
     method="host" (the default): ``mean_and_cov(x_fit, lengths) -> (mu (M,), cov (M, M))`` injects
@@ -72,7 +73,11 @@ def sample_posterior(x_known, y_known, e_known, x_fit, lengths, n_draws, seed=No
     normals are default_rng(seed).standard_normal((n_draws, M)), exactly draws_from's, so a seed
     means the same normals on both paths. ``jitters`` is the ladder (ascending, >= 0). info: "mu",
     "jitter", "tries"; no "cov".
+
+    ``kernel``: the covariance kernel, "se" (default), "matern32" or "matern52" (gpfit.kernels), set on the context on every call. An injected
+    ``mean_and_cov`` brings its own.
     """
+    kernel_kind(kernel)
     if method not in METHODS:
         raise ValueError(f"method must be one of {METHODS}, not {method!r}")
     x_fit = np.asarray(x_fit, dtype=np.float64)
@@ -88,6 +93,7 @@ def sample_posterior(x_known, y_known, e_known, x_fit, lengths, n_draws, seed=No
         if ctx is None:
             ctx = default_context()
         ctx.set_data(x_known, y_known, e_known)
+        use_kernel(ctx, kernel)
         mu, draws, info = ctx.posterior_draws(lengths, x_fit, z, jitters=jitters)
         info["mu"] = mu
         return draws, info
@@ -98,6 +104,7 @@ def sample_posterior(x_known, y_known, e_known, x_fit, lengths, n_draws, seed=No
         if ctx is None:
             ctx = default_context()
         ctx.set_data(x_known, y_known, e_known)
+        use_kernel(ctx, kernel)
         mu, cov = ctx.predict_cov(lengths, x_fit)
     else:
         mu, cov = mean_and_cov(x_fit, lengths)

@@ -13,7 +13,8 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._lib import default_comm, default_context
+from ._lib import default_comm, default_context, use_kernel
+from .kernels import kernel_kind
 
 NUM_PARTICLES = 40      # find_len_scales.py:50
 MAX_ITER = 500          # :51
@@ -236,12 +237,15 @@ def prepare(x_known, y_known, e_known, *, max_points=MAX_POINTS, verbose=True, c
 
 
 def make_scorer(x_known, y_known, e_known, sigma_vals, expected, lower, upper, *, evaluator=None, ctx=None,
-                comm=None):
+                comm=None, kernel="se"):
     """Sharded batch objective: gpf_eval_batch(_sharded) on this GPU, or an injected per-particle
-    evaluator. comm: a gpfit.Comm, or None for the launcher's group (WORLD_SIZE > 1) if any."""
+    evaluator. comm: a gpfit.Comm, or None for the launcher's group (WORLD_SIZE > 1) if any. kernel: the
+    covariance kernel every rank sets on its context ("se", "matern32" or "matern52")."""
+    kernel_kind(kernel)
     if evaluator is None:
         dev = ctx if ctx is not None else default_context()
         dev.set_data(x_known, y_known, e_known)
+        use_kernel(dev, kernel)
         dev.set_grid(sigma_vals, expected, lower, upper)
         comm = comm if comm is not None else default_comm(dev)
         return ShardedScorer(dev.eval_batch, comm, dev)
@@ -255,7 +259,7 @@ def make_scorer(x_known, y_known, e_known, sigma_vals, expected, lower, upper, *
 
 def particle_swarm(x_known, y_known, e_known, PSO_progress, *, num_particles=NUM_PARTICLES,
                    max_iter=MAX_ITER, max_points=MAX_POINTS, init_positions=None, seed=None,
-                   evaluator=None, trace=None, ctx=None, comm=None, verbose=True):
+                   evaluator=None, trace=None, ctx=None, comm=None, verbose=True, kernel="se"):
     """len_scale_opt body (find_len_scales.py:22-150) with a batched evaluator.
 
     ``evaluator(args_list) -> scores`` (reference-style per-particle args, used
@@ -263,15 +267,17 @@ def particle_swarm(x_known, y_known, e_known, PSO_progress, *, num_particles=NUM
     on this process's GPU. Either way batches are sharded over the ranks of ``comm`` (default:
     the launcher's group when WORLD_SIZE > 1, gpfit.default_comm).
     Returns (global_best_position, info) where info holds the final score,
-    restart count and evaluation count.
+    restart count and evaluation count. ``kernel``: the covariance kernel of the objective ("se",
+    "matern32" or "matern52"), set on the context of every rank; an injected evaluator brings its own.
     """
+    kernel_kind(kernel)
     if evaluator is None and ctx is None:  # the GPU path: this process's context, the KMeans fit included
         ctx = default_context()
     x_known, y_known, e_known, lower, upper, sigma_vals, expected = prepare(
         x_known, y_known, e_known, max_points=max_points, verbose=verbose, ctx=ctx if evaluator is None else None)
 
     score = make_scorer(x_known, y_known, e_known, sigma_vals, expected, lower, upper,
-                        evaluator=evaluator, ctx=ctx, comm=comm)
+                        evaluator=evaluator, ctx=ctx, comm=comm, kernel=kernel)
     seed = share_seed(seed, score.comm)
     if seed is not None:
         np.random.seed(seed)

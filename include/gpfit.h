@@ -13,7 +13,8 @@
  *                   batch_size=N) (GP_func.py:12-45, called at :159).
  *   gpf_predict     replaces GP(x_known,y_known,e_known,x_fit,lengths,batch_size)
  *                   (GP_func.py:12-45) for arbitrary query points (GP_fit.py:32).
- *   gpf_kernel      replaces kernel_func(x1,x2,l) (GP_func.py:49-65).
+ *   gpf_kernel      replaces kernel_func(x1,x2,l) (GP_func.py:49-65) under the
+ *                   default kernel, se.
  *
  * Conventions (mirroring the reference):
  *   - all floating point is IEEE fp64;
@@ -69,6 +70,25 @@ const char* gpf_last_error(gpf_ctx* ctx);
 int gpf_set_data(gpf_ctx* ctx, const double* x_dN, const double* y,
                  const double* e, int64_t N, int d);
 
+/* The covariance function of every call on this context (the context's kernel). With
+ * a_k = x_k / l_k and r2 = sum_k (a_ik - a_jk)^2, formed and clamped at 0 as kernel_func does
+ * (GP_func.py:56-63), K_ij = phi(r2):
+ *   GPF_KERNEL_SE       (default)  exp(-r2 / 2)                       the reference's kernel_func
+ *   GPF_KERNEL_MATERN32            (1 + s) exp(-s),            s = sqrt(3 r2)
+ *   GPF_KERNEL_MATERN52            (1 + s + s^2 / 3) exp(-s),  s = sqrt(5 r2)
+ * phi(0) = 1 for all three: the prior variance of every model below stays 1. The length-scale
+ * gradients use dK_ij/dl_k = psi(r2) (x_ik - x_jk)^2 / l_k^3 with psi = -2 phi'(r2): phi, 3 exp(-s)
+ * and (5/3) (1 + s) exp(-s)
+ * (psi_ij in the gradient formulas below; K_ij itself under se).
+ * Needs no data. The kind is a model choice, not a property of the points: it persists across
+ * gpf_set_data. GPF_BAD_ARG for a null context, a null kind pointer or an unknown kind; the kind set
+ * before stays. */
+#define GPF_KERNEL_SE 0
+#define GPF_KERNEL_MATERN32 1
+#define GPF_KERNEL_MATERN52 2
+int gpf_set_kernel(gpf_ctx* ctx, int kind);
+int gpf_get_kernel(gpf_ctx* ctx, int* kind);
+
 /* Objective grid and search box: sigma_vals/expected are the K-point grid of
  * find_len_scales.py:66-67 (K = 1000 in the reference), lo/hi the (d,) bounds of
  * :56-61. 2 <= K <= 4096; sigma_vals and expected hold K doubles, lo and hi d.
@@ -104,7 +124,7 @@ int gpf_predict(gpf_ctx* ctx, const double* ls, const double* xfit_dM,
  *   mu_M[q] = K_s[:, q]^T alpha — bitwise gpf_predict's mean for the same inputs;
  *   cov_MM  = K_ss - V^T V, V = L^-1 K_s: the full M x M row-major matrix, both triangles
  *             written, exactly symmetric (the upper triangle is a copy of the lower).
- * K_ss is kernel_func(xfit, xfit, l) with the diagonal exactly 1.0 (the prior variance,
+ * K_ss is the context's kernel (gpf_set_kernel; kernel_func under se) at (xfit, xfit, l) with the diagonal exactly 1.0 (the prior variance,
  * GP_func.py:34). The diagonal of cov_MM is NOT clipped at 1e-12 as gpf_predict's variance is
  * (GP_func.py:39): where a query point coincides with another one or with a noise-free training
  * point it can come out a few 1e-14 below zero; a caller that factorises cov_MM adds a jitter
@@ -125,7 +145,7 @@ int gpf_predict_cov(gpf_ctx* ctx, const double* ls, const double* xfit_dM, int64
  *   mean_R[r] = sum_q w[r,q] mu_q                               (A mu)
  *   cov_RR    = A K_ss A^T - V_A^T V_A, V_A = L^-1 (K_s A^T)    (A Sigma A^T, Sigma as gpf_predict_cov's)
  *   prior_RR  = A K_ss A^T (nullable): the prior covariance of the functionals.
- * The model is gpf_predict_cov's: K_ss = kernel_func(xfit, xfit, l) with the diagonal exactly 1.0, and
+ * The model is gpf_predict_cov's: K_ss = the context's kernel at (xfit, xfit, l) with the diagonal exactly 1.0, and
  * cov_RR is not clipped. cov_RR and prior_RR are full R x R row-major matrices, both triangles
  * written, exactly symmetric (the upper triangle is a copy of the lower).
  * The query axis is chunked: `chunk` query points per pass, rounded up to 128 and capped at 65536;
@@ -220,7 +240,8 @@ int gpf_posterior_draws(gpf_ctx* ctx, const double* ls, const double* xfit_dM, i
                         double* mu_M, double* draws_SM, double* chol_MM,
                         double* jitter_used, int* tries);
 
-/* kernel_func(x1, x2, l) (GP_func.py:49-65): out is (N1, N2) row-major. */
+/* The context's kernel (gpf_set_kernel) at (x1, x2, l): out is (N1, N2) row-major. It is
+ * kernel_func(x1, x2, l) (GP_func.py:49-65) only for se, the default. */
 int gpf_kernel(gpf_ctx* ctx, const double* x1_dN1, int64_t N1,
                const double* x2_dN2, int64_t N2, int d, const double* l,
                double* out);
@@ -230,11 +251,12 @@ int gpf_kernel(gpf_ctx* ctx, const double* x1_dN1, int64_t N1,
 int gpf_log_marginal_likelihood(gpf_ctx* ctx, const double* ls, double* out);
 
 /* Batched log marginal likelihood and its gradient in the length scales (fixed amplitude 1,
- * fixed noise e^2, ARD squared-exponential), the objective of a maximum-marginal-likelihood fit
+ * fixed noise e^2, the context's ARD kernel), the objective of a maximum-marginal-likelihood fit
  * (gpfit.mle.fit_lml). ls_Pd is (P, d) row-major. Needs gpf_set_data only (no grid, no box).
  *   lml_P[p]     = -1/2 y^T alpha - sum log L_ii - N/2 log(2 pi)
- *   grad_Pd[p,k] = dLML/dl_k = sum_{i>j} (alpha_i alpha_j - W_ij) K_ij (x_ik - x_jk)^2 / l_k^3,
- *                  W = Kn^-1, K the noise-free kernel (nullable: without it the gradient pass
+ *   grad_Pd[p,k] = dLML/dl_k = sum_{i>j} (alpha_i alpha_j - W_ij) psi_ij (x_ik - x_jk)^2 / l_k^3,
+ *                  W = Kn^-1, psi the kernel's derivative weight (gpf_set_kernel; K_ij, the
+ *                  noise-free kernel, under se) (nullable: without it the gradient pass
  *                  is not run)
  *   status_P[p]  = GPF_OK or GPF_NOT_PD (nullable)
  * Everything is computed on the device from the factorisation's L, U = L^-1 and alpha; the
@@ -256,9 +278,10 @@ int gpf_lml_batch(gpf_ctx* ctx, const double* ls_Pd, int P, double* lml_P, doubl
  *                  (nullable)
  *   sd_PN[p,i]   = sqrt(1 / w_i): its predictive sd, e_i^2 included, not clipped (nullable)
  *   lpd_P[p]     = sum_i [1/2 log w_i - 1/2 alpha_i^2 / w_i] - N/2 log(2 pi)
- *   grad_Pd[p,k] = dlpd/dl_k = sum_{i>j} (u_i alpha_j + u_j alpha_i - 2 G_ij) K_ij (x_ik - x_jk)^2 / l_k^3,
+ *   grad_Pd[p,k] = dlpd/dl_k = sum_{i>j} (u_i alpha_j + u_j alpha_i - 2 G_ij) psi_ij (x_ik - x_jk)^2 / l_k^3,
  *                  c_i = alpha_i / w_i, g_i = 1/2 (1 + alpha_i^2 / w_i) / w_i, u = W c, G = W diag(g) W,
- *                  K the noise-free kernel (nullable: without it neither O(N^3) pass is run)
+ *                  psi the kernel's derivative weight (gpf_set_kernel; K_ij, the noise-free kernel,
+ *                  under se) (nullable: without it neither O(N^3) pass is run)
  *   status_P[p]  = GPF_OK or GPF_NOT_PD (nullable)
  * The pull (y_i - mu_i) / sd_i = alpha_i / sqrt(w_i) is N(0, 1) under the model.
  * Everything is computed on the device from the factorisation's U = L^-1 and its partial sums of
@@ -284,7 +307,7 @@ int gpf_loo_batch(gpf_ctx* ctx, const double* ls_Pd, int P, double* lpd_P, doubl
  * K build adds e_i^2 r on the diagonal); with Lt = chol(Kt), Wt = Kt^-1, alt = Wt y, wt_i = Wt_ii,
  * Q = y^T alt and S = sum_i e_i^2 (alt_i^2 / a^2 - wt_i):
  *   lml_P[p]         = -Q / (2 a^2) - sum_i log Lt_ii - N log a - N/2 log(2 pi)
- *   grad_Pd2[p,k<d]  = sum_{i>j} (alt_i alt_j / a^2 - Wt_ij) K_ij (x_ik - x_jk)^2 / l_k^3
+ *   grad_Pd2[p,k<d]  = sum_{i>j} (alt_i alt_j / a^2 - Wt_ij) psi_ij (x_ik - x_jk)^2 / l_k^3
  *   grad_Pd2[p,d]    = dLML/da = (Q / a^2 - N) / a - (s^2 / a^3) S
  *   grad_Pd2[p,d+1]  = dLML/ds = (s / a^2) S                        (grad_Pd2 nullable: no O(N^3) pass)
  *   q_P[p]           = Q: for fixed (l, r) the best amplitude is a^2 = Q / N (nullable)
@@ -322,7 +345,7 @@ int gpf_set_basis(gpf_ctx* ctx, const double* H_mN, int m);
  * Z = U H^T, At = Z^T Z = H Kt^-1 H^T = La La^T, Zo = Z La^-T, t = Zo^T z, zr = z - Zo t, Q' = zr^T zr,
  * Bt = Zo^T U, Pt = U^T U - Bt^T Bt, at = Pt y, pt_i = Pt_ii and S' = sum_i e_i^2 (at_i^2 / a^2 - pt_i):
  *   lml_P[p]         = -Q' / (2 a^2) - sum log Lt_ii - sum log La_rr - (N - m) log a - (N - m)/2 log(2 pi)
- *   grad_Pd2[p,k<d]  = sum_{i>j} (at_i at_j / a^2 - Pt_ij) K_ij (x_ik - x_jk)^2 / l_k^3
+ *   grad_Pd2[p,k<d]  = sum_{i>j} (at_i at_j / a^2 - Pt_ij) psi_ij (x_ik - x_jk)^2 / l_k^3
  *   grad_Pd2[p,d]    = dLML/da = (Q' / a^2 - (N - m)) / a - (s^2 / a^3) S'
  *   grad_Pd2[p,d+1]  = dLML/ds = (s / a^2) S'                       (grad_Pd2 nullable: no O(N^3) pass)
  *   beta_Pm[p]       = La^-T t, the generalised-least-squares coefficients; they do not depend on a (nullable)
